@@ -11,8 +11,11 @@ at a fixed expansion point followed by the sampled-KL value/gradient mean
 and CPU do identical work.  Samples are sharded over ranks with shareRange:
 per-GPU work is fixed (weak scaling).
 
-Prints ONE JSON line (rank 0).  See DESIGN.md §Measurement for the roofline
-and CPU-baseline definitions.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps
+and prints the headline figure (`--dump-outputs DIR` also stores what the last
+timed step returned); `--full` adds the per-kernel table, roofline, demo
+controllers, CPU baseline and the ranks' checks.  See DESIGN.md §Measurement
+for the roofline and CPU-baseline definitions.
 """
 import argparse
 import collections
@@ -72,6 +75,13 @@ def parse():
     p.add_argument("--backend", choices=["nccl", "gloo", "none"], default=None,
                    help="process-group backend (default: nccl = RCCL on a GPU, also at N = 1; gloo on CPU "
                         "at N > 1; none: no communicator, N = 1 only)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything beside the headline figure: the per-kernel "
+                        "table and roofline, the demo-controller step, the CPU baseline, the ranks' consistency "
+                        "check and the timed KL all-reduce (a plain run leaves those keys of the line null)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (KL value, KL gradient, the samples) as "
+                        "DIR/<name>.npy, float64, at most 64 MB in all (large arrays: a fixed seeded sample)")
     a = p.parse_args()
     cfg = CONFIGS[a.config]
     if a.size is None:
@@ -740,6 +750,42 @@ class _TimedComm:
         return t
 
 
+DUMP_BUDGET = 60 * 2**20   # bytes of array data per dump (the limit is 64 MB)
+DUMP_SMALL = 2**20         # arrays up to this many bytes are written whole
+
+
+def _field_arrays(prefix, field):
+    """(name, float64 host array) of every key of a MultiField / of a Field"""
+    if hasattr(field, "keys"):
+        return [(f"{prefix}_{k}", field[k].val.detach().cpu().numpy().astype(np.float64)) for k in field.keys()]
+    return [(prefix, field.val.detach().cpu().numpy().astype(np.float64))]
+
+
+def dump_outputs(path, kl, rank, ws):
+    """What the last timed step handed back, as <path>/<name>.npy (float64):
+    the KL value and gradient (the same on every rank: rank 0 writes them)
+    and this rank's samples under their global indices.  Arrays above 1 MiB
+    share what is left of the budget equally: each is cut to the same number
+    of entries, picked by a generator seeded with the array's size, so two
+    runs with the same arguments write the same entries."""
+    os.makedirs(path, exist_ok=True)
+    arrs = []
+    if rank == 0:
+        arrs.append(("kl_value", np.array([kl.value], dtype=np.float64)))
+        arrs += _field_arrays("kl_gradient", kl.gradient)
+    sl = kl.samples
+    for i, gi in enumerate(sl.local_indices):
+        arrs += _field_arrays(f"sample{gi}", sl.local_item(i))
+    big = [a for _, a in arrs if a.nbytes > DUMP_SMALL]
+    left = DUMP_BUDGET // max(ws, 1) - sum(a.nbytes for _, a in arrs if a.nbytes <= DUMP_SMALL)
+    cap = max(left // (8 * len(big)), 1) if big else 0
+    for name, a in arrs:
+        if a.nbytes > DUMP_SMALL and a.size > cap:
+            idx = np.sort(np.random.default_rng(a.size).integers(0, a.size, cap))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _json_stdout():
     """stdout carries ONE JSON line: RCCL prints a banner ("RCCL version :
     ...") to fd 1 when its first communicator comes up, and libraries may
@@ -804,6 +850,10 @@ def main():
         dist.all_reduce(t[0:1], op=dist.ReduceOp.MAX)
         dist.all_reduce(t[1:2], op=dist.ReduceOp.SUM)
         el, iters = float(t[0]), float(t[1])
+        dist_info = {"backend": dist.get_backend()}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, kl, rank, ws)
+    if has_pg and args.full:
         # every rank drew its share and holds the same KL: a rank that
         # disagrees fails the run (non-zero exit on every rank)
         per_rank = [int(c) for c in comm.allgather(kl.samples.n_local_samples)]
@@ -831,14 +881,17 @@ def main():
     samples = 2 * nsamp * args.steps
     sps = samples / el
     cgps = iters / el
-    kp, cgit = kernel_probe(ift, cf, R, lh, pos, args.samples_per_gpu) if torch.cuda.is_available() \
+    # everything from here to the result line runs with --full only
+    kp, cgit = kernel_probe(ift, cf, R, lh, pos, args.samples_per_gpu) if args.full and torch.cuda.is_available() \
         else (None, None)
     roof = roofline_of(kp, cgit, cf, R, args.config) if kp else None
     demo = None
-    if not args.no_demo and torch.cuda.is_available() and args.config == "C3":
+    if args.full and not args.no_demo and torch.cuda.is_available() and args.config == "C3":
         demo = demo_step(ift, lh, pos, nsamp, comm, R)
     cpu = None
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline and args.config != "C3":
+    if not args.full:
+        pass
+    elif rank == 0 and ws == 1 and not args.no_cpu_baseline and args.config != "C3":
         lat0 = {k: pos[k].val.cpu().numpy() for k in cf.domain.keys()}
         cpu = cpu_baseline_config(args, lat0, n, int(iters), samples)
     elif rank == 0 and ws == 1 and not args.no_cpu_baseline:

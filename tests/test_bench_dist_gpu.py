@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_three_ranks_gloo(dev):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--backend", "gloo", "--size", "128",
            "--nlos", "500", "--samples-per-gpu", "1", "--lin-iters", "10", "--newton-iters", "1",
-           "--newton-cg-max", "5", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-demo"]
+           "--newton-cg-max", "5", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-demo"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=ROOT,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-3000:]

@@ -101,7 +101,7 @@ def test_bench_two_ranks(dev, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--size", "256", "--nlos", "1024",
            "--samples-per-gpu", "1", "--steps", "1", "--warmup", "1", "--lin-iters", "5", "--newton-iters", "1",
-           "--newton-cg-max", "5", "--backend", "gloo", "--no-demo", "--no-cpu-baseline"]
+           "--newton-cg-max", "5", "--backend", "gloo", "--full", "--no-demo", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

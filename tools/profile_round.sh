@@ -7,6 +7,9 @@
 tag=${1:-cur}
 R=$PWD
 mkdir -p gpurun_out
+# the two whole-benchmark lines (bench.py --full) go to $OUT
+OUT=${OUT:-$R/bench_out}
+mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/pmc_fetch $R/gpurun_out/pmc_write
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/pmc_fetch -o run -- python3 $R/tools/pmc_probe.py > $R/gpurun_out/pmc1.log 2>&1 || exit $?
@@ -14,7 +17,7 @@ timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $R/gpurun_
 cd $R
 python3 tools/pmc_summary.py gpurun_out > gpurun_out/pmc_summary.log || exit $?
 cp profiles/pmc_traffic.json gpurun_out/pmc_traffic.json
-timeout -k 10 400 python3 -u bench.py > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err || exit $?
+timeout -k 10 400 python3 -u bench.py --full > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err || exit $?
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/replay_$tag -o run -- python3 $R/tools/replay_probe.py > $R/gpurun_out/replay_$tag.log 2>&1 || exit $?
 cd $R
@@ -25,5 +28,5 @@ LAZY_CHUNK=1 REPLAYS=19 timeout -k 10 300 rocprofv3 --kernel-trace --stats --out
 cd $R
 python3 tools/trace_labels.py gpurun_out/replayl_$tag/run_kernel_trace.csv 19 > gpurun_out/trace_labels_lazy_$tag.json || exit $?
 cd /tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$tag -o run -- python3 $R/bench.py --no-cpu-baseline > $R/gpurun_out/bench_${tag}_under_rocprof.json 2> $R/gpurun_out/prof_$tag.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$tag -o run -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/bench_${tag}_under_rocprof.json 2> $OUT/prof_$tag.err
 echo "done rc=$?"
