@@ -451,6 +451,25 @@ int nft_los_adjoint_ex(const nft_los_plan* plan, const void* y, const void* cols
                        const void* rowscale, int64_t rowscale_stride, void* out, int dtype,
                        double scale, int nvec, int64_t y_stride, int64_t out_stride,
                        hipStream_t stream);
+/* The adjoint with a pointwise branch on the same grid: the middle of a joint
+ * likelihood's sampling metric, M1^T C1 M1 + diag(addw), whose branches the
+ * reference sums operator by operator (_LikelihoodSum.get_transformation,
+ * src/operators/energy_operators.py:268-285, inside SandwichOperator).
+ *   out[v, p] = L[v, p] + addw_v[p] * addx[v, p]
+ * with L what nft_los_adjoint_ex stores (same entries, order and fp64
+ * accumulation) before its cast; the product and the sum are two separately
+ * rounded fp64 operations, then the cast to the storage type.  addw_v = addw
+ * + v * addw_stride (stride 0: one weight vector for all), addx likewise.
+ * qpart (NULL: none): qpart[v * qstride + b] = sum over the pixels of block b
+ * of addw_v[p] * addx[v, p]^2 in fp64, b < nft_los_add_blocks(plan) (one
+ * block per box, every grid pixel in exactly one; the order does not depend
+ * on nvec).  A plan without boxes has no pixels: NFT_OK, nothing written. */
+int nft_los_add_blocks(const nft_los_plan* plan);
+int nft_los_adjoint_add(const nft_los_plan* plan, const void* y, const void* colscale,
+                        const void* rowscale, int64_t rowscale_stride, void* out, int dtype,
+                        double scale, int nvec, int64_t y_stride, int64_t out_stride,
+                        const void* addw, int64_t addw_stride, const void* addx,
+                        int64_t addx_stride, double* qpart, int64_t qstride, hipStream_t stream);
 
 /* ---- curvature from the data space ------------------------------------ */
 /* For a CG metric shift * 1 + J^T R^T C R J (the LOS sampling metric) the

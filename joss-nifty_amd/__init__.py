@@ -54,8 +54,8 @@ from .operators.sampling_enabler import SamplingEnabler
 from .operators.sandwich_operator import SandwichOperator
 from .operators.scaling_operator import ScalingOperator
 from .operators.simple_linear_operators import (ConjugationOperator, FieldAdapter, GeometryRemover,
-                                                NullOperator, PartialExtractor, Realizer, VdotOperator,
-                                                ducktape)
+                                                NullOperator, PartialExtractor, PrependKey, Realizer,
+                                                VdotOperator, ducktape)
 from .operators.sum_operator import SumOperator
 from .operators.value_inserter import ValueInserter
 from .sugar import (domain_union, exp, from_random, full, is_fieldlike, is_linearization, is_operator, log,

@@ -62,6 +62,9 @@ SIGNATURES = {
     "nft_los_forward_quad_batched": (_i, [_p, _p, _p, _p, _p, _p, _i, _d, _i, _i64, _i64, _p, _i64, _p]),
     "nft_los_forward_ex": (_i, [_p, _p, _p, _i64, _p, _p, _p, _i, _d, _i, _i64, _i64, _p, _i64, _p]),
     "nft_los_adjoint_ex": (_i, [_p, _p, _p, _p, _i64, _p, _i, _d, _i, _i64, _i64, _p]),
+    "nft_los_add_blocks": (_i, [_p]),
+    "nft_los_adjoint_add": (_i, [_p, _p, _p, _p, _i64, _p, _i, _d, _i, _i64, _i64, _p, _i64, _p, _i64, _p, _i64,
+                                 _p]),
     "nft_cg_dd_blocks": (_i, [_i64]),
     "nft_cg_direction_dd_batched": (_i, [_p, _p, _i64, _i64, _i, _i, _p, _d, _p, _i64, _p]),
     "nft_fold_partials": (_i, [_p, _i, _i, _p, _i64, _p]),
@@ -653,6 +656,35 @@ def los_adjoint_ex(plan, y, out, colscale=None, rowscale=None, scale=1.0):
     rss = _pixel_scale_stride(rowscale, k, out[0].numel())
     _check(lib.nft_los_adjoint_ex(ctypes.byref(plan), ptr(y), ptr(colscale), ptr(rowscale), rss, ptr(out),
                                   dtype_code(y.dtype), float(scale), k, y[0].numel(), out[0].numel(), stream_ptr()))
+    return out
+
+
+def los_adjoint_add(plan, y, out, addw, addx, colscale=None, rowscale=None, scale=1.0, qpart=None):
+    """out[b] = scale * rowscale[b] * R^T (colscale * y[b]) + addw[b] * addx[b]
+    (nft_los_adjoint_add): addw one shared pixel vector or one per vector,
+    addx one per vector; qpart (k, >= nft_los_add_blocks) fp64 rows receive
+    the per-box partials of sum addw * addx^2, or None."""
+    lib = load()
+    require_device(y, out, colscale, rowscale, addw, addx)
+    k = y.shape[0]
+    npix = out[0].numel()
+    if not (y.is_contiguous() and out.is_contiguous() and addx.is_contiguous()):
+        raise NativeError("los_adjoint_add: contiguous y, out and addx required")
+    if addw.dtype != y.dtype or addx.dtype != y.dtype or out.dtype != y.dtype:
+        raise NativeError("los_adjoint_add: y, out, addw and addx share one dtype")
+    if addx.numel() != k * npix:
+        raise NativeError(f"los_adjoint_add: addx holds {addx.numel()} elements for {k} vectors of {npix} pixels")
+    rss = _pixel_scale_stride(rowscale, k, npix)
+    aws = _pixel_scale_stride(addw, k, npix)
+    qs = 0
+    if qpart is not None:
+        if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1
+                and qpart.shape[0] >= k and qpart.shape[1] >= lib.nft_los_add_blocks(ctypes.byref(plan))):
+            raise NativeError("qpart: (k, >= nft_los_add_blocks) fp64 device rows with unit element stride")
+        qs = qpart.stride(0)
+    _check(lib.nft_los_adjoint_add(ctypes.byref(plan), ptr(y), ptr(colscale), ptr(rowscale), rss, ptr(out),
+                                   dtype_code(y.dtype), float(scale), k, y[0].numel(), npix, ptr(addw), aws,
+                                   ptr(addx), npix, ptr(qpart), qs, stream_ptr()))
     return out
 
 

@@ -25,6 +25,7 @@
 // All reductions run in a fixed order: deterministic, no atomics.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "nft_api_internal.hpp"
 
@@ -399,13 +400,36 @@ __device__ __forceinline__ void los_fold_rhs(const LosFold& f, int r, double* sh
 // fp32 weight) are staged in LDS once; every pixel thread sums its run for
 // all K vectors in registers from the per-vector line tables.  Per vector the
 // products and their order are those of K = 1 (bitwise).
-template <typename T, typename IDX, int K, bool VEC = false>
+//
+// ADD (nft_los_adjoint_add): a pointwise branch joins the store -- out = L +
+// w * x per pixel, L the value the plain kernel stores before its cast, the
+// product and the sum rounded separately in fp64 -- and the box's partial of
+// sum w * x^2 goes to qpart[box]: the four waves' shuffle trees, then the wave
+// totals in order, per vector (the same for every K).  w and x are read once,
+// after the entry loop (no registers held across it); the line table, free by
+// then, carries the wave totals.
+template <typename T>
+struct LosAdd {
+  const T* w;
+  const T* x;
+  double* qpart;
+  long long ws, xs, qs;
+};
+
+template <typename T, typename IDX, int K, bool VEC = false, bool ADD = false>
 __global__ __launch_bounds__(256) void los_adj_boxes(nft_los_plan p, const IDX* __restrict__ lidx,
                                                      const T* __restrict__ yv, const T* __restrict__ cs,
                                                      const T* __restrict__ rs, T* __restrict__ out, double scale,
                                                      long long ys, long long os, long long rss, int kv,
-                                                     LosFold fold) {
+                                                     std::conditional_t<ADD, LosAdd<T>, LosFold> tail) {
 #pragma clang fp contract(off)
+  // the last argument: the carried fold, or the pointwise branch
+  LosFold fold{nullptr, nullptr, 0, 0, 0};
+  LosAdd<T> add{};
+  if constexpr (ADD)
+    add = tail;
+  else
+    fold = tail;
   constexpr int PER = LOS_CH_A / 256;
   // line table: 256 lines per vector cover every box of an 8-bit-index plan
   // (boxes with more lines read y from global memory); sized per K so that
@@ -552,13 +576,51 @@ __global__ __launch_bounds__(256) void los_adj_boxes(nft_los_plan p, const IDX* 
       }
     }
   }
-  if (ok) {
-    // pixel-side scale: shared by the vectors (rss = 0) or one per vector
+  if constexpr (!ADD) {
+    if (ok) {
+      // pixel-side scale: shared by the vectors (rss = 0) or one per vector
 #pragma unroll
-    for (int v = 0; v < K; ++v) {
-      double o = acc[v] * scale;
-      if (rs) o *= rsv[v];
-      if (v < kv) out[v * os + px] = (T)o;
+      for (int v = 0; v < K; ++v) {
+        double o = acc[v] * scale;
+        if (rs) o *= rsv[v];
+        if (v < kv) out[v * os + px] = (T)o;
+      }
+    }
+  } else {
+    const bool red = add.qpart != nullptr;  // uniform over the block
+    if (red) __syncthreads();               // the line table is free
+    // four vectors at a time: their eight loads in flight together, and no
+    // more (all sixteen of K = 8 cost 44 registers and two waves per SIMD)
+    constexpr int G = K < 4 ? K : 4;
+#pragma unroll
+    for (int v0 = 0; v0 < K; v0 += G) {
+      double q[G];
+#pragma unroll
+      for (int j = 0; j < G; ++j) {
+        const int v = v0 + j;
+        q[j] = 0.0;
+        if (ok && v < kv) {
+          double o = acc[v] * scale;
+          if (rs) o *= rsv[v];
+          const double w = (double)add.w[v * add.ws + px], x = (double)add.x[v * add.xs + px];
+          const double wx = w * x;
+          out[v * os + px] = (T)(o + wx);
+          q[j] = wx * x;
+        }
+      }
+      if (red) {
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+#pragma unroll
+          for (int off = 32; off > 0; off >>= 1) q[j] += __shfl_down(q[j], off, 64);
+          if ((t & 63) == 0) yl[(t >> 6) * K + v0 + j] = q[j];
+        }
+      }
+      if constexpr (K > 4) __builtin_amdgcn_sched_barrier(0);
+    }
+    if (red) {
+      __syncthreads();
+      if (t < K && t < kv) add.qpart[t * add.qs + box] = ((yl[t] + yl[K + t]) + yl[2 * K + t]) + yl[3 * K + t];
     }
   }
 }
@@ -591,6 +653,22 @@ static void adj_boxes_k(const nft_los_plan* p, const IDX* li, const T* y, const 
   }
   hipLaunchKernelGGL((los_adj_boxes<T, IDX, K>), grid, dim3(256), 0, s, *p, li, y, cs, rs, out, scale, ys, os, rss,
                      kv, fold);
+}
+
+template <typename T, typename IDX, int K>
+static void adj_boxes_add_k(const nft_los_plan* p, const IDX* li, const T* y, const T* cs, const T* rs, T* out,
+                            double scale, long long ys, long long os, long long rss, int kv, hipStream_t s,
+                            const LosAdd<T>& add) {
+  const dim3 grid((unsigned)p->nbox);
+  if constexpr (K > 1 && sizeof(IDX) == 1) {
+    if (p->box_ent_adj) {
+      hipLaunchKernelGGL((los_adj_boxes<T, IDX, K, true, true>), grid, dim3(256), 0, s, *p, li, y, cs, rs, out, scale,
+                         ys, os, rss, kv, add);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((los_adj_boxes<T, IDX, K, false, true>), grid, dim3(256), 0, s, *p, li, y, cs, rs, out, scale,
+                     ys, os, rss, kv, add);
 }
 
 // vectors are processed in groups of 8 / 4 / 2 / 1 (template sizes); a
@@ -675,6 +753,47 @@ static int los_adjoint_t(const nft_los_plan* p, const void* y, const void* cs, c
   else
     los_adjoint_idx<T, unsigned short>(p, (const unsigned short*)p->ent_lidx, y, cs, rs, out, scale, K, ys, os, s,
                                        rss, fold);
+  NFT_HIP_CHECK(hipGetLastError());
+  return NFT_OK;
+}
+
+// nft_los_adjoint_add: the vector groups of los_adjoint_idx, each launch with
+// its vectors' weights, inputs and partial rows
+template <typename T, typename IDX>
+static void los_adjoint_add_idx(const nft_los_plan* p, const IDX* li, const void* y, const void* cs, const void* rs,
+                                void* out, double scale, int K, long long ys, long long os, long long rss,
+                                const LosAdd<T>& add, hipStream_t s) {
+  for (int v = 0; v < K;) {
+    const int g = kgroup(K - v), kv = std::min(g, K - v);
+    const T* yv = (const T*)y + v * ys;
+    const T* rv = rs ? (const T*)rs + v * rss : nullptr;
+    T* ov = (T*)out + v * os;
+    const LosAdd<T> av{add.w + v * add.ws, add.x + v * add.xs, add.qpart ? add.qpart + v * add.qs : nullptr,
+                       add.ws, add.xs, add.qs};
+    switch (g) {
+      case 8: adj_boxes_add_k<T, IDX, 8>(p, li, yv, (const T*)cs, rv, ov, scale, ys, os, rss, kv, s, av); break;
+      case 4: adj_boxes_add_k<T, IDX, 4>(p, li, yv, (const T*)cs, rv, ov, scale, ys, os, rss, kv, s, av); break;
+      case 2: adj_boxes_add_k<T, IDX, 2>(p, li, yv, (const T*)cs, rv, ov, scale, ys, os, rss, kv, s, av); break;
+      default: adj_boxes_add_k<T, IDX, 1>(p, li, yv, (const T*)cs, rv, ov, scale, ys, os, rss, 1, s, av); break;
+    }
+    v += kv;
+  }
+}
+
+template <typename T>
+static int los_adjoint_add_t(const nft_los_plan* p, const void* y, const void* cs, const void* rs, void* out,
+                             double scale, int K, long long ys, long long os, long long rss, const void* addw,
+                             long long aws, const void* addx, long long axs, double* qpart, long long qs,
+                             hipStream_t s) {
+  if (p->nbox <= 0) return NFT_OK;  // no boxes, no pixels
+  prof_mark(s, "los_adj_boxes_add");
+  const LosAdd<T> add{(const T*)addw, (const T*)addx, qpart, aws, axs, qs};
+  if (p->lidx8)
+    los_adjoint_add_idx<T, unsigned char>(p, (const unsigned char*)p->ent_lidx, y, cs, rs, out, scale, K, ys, os, rss,
+                                          add, s);
+  else
+    los_adjoint_add_idx<T, unsigned short>(p, (const unsigned short*)p->ent_lidx, y, cs, rs, out, scale, K, ys, os,
+                                           rss, add, s);
   NFT_HIP_CHECK(hipGetLastError());
   return NFT_OK;
 }
@@ -816,6 +935,30 @@ int nft_los_adjoint_ex(const nft_los_plan* p, const void* y, const void* colscal
     return los_adjoint_t<float>(p, y, colscale, rowscale, out, scale, nvec, y_stride, out_stride, stream,
                                 rowscale_stride);
   set_last_error("nft_los_adjoint_ex: bad dtype %d", dtype);
+  return NFT_ERR_ARG;
+}
+
+int nft_los_add_blocks(const nft_los_plan* p) { return (p && p->nbox > 0) ? (int)p->nbox : 0; }
+
+int nft_los_adjoint_add(const nft_los_plan* p, const void* y, const void* colscale, const void* rowscale,
+                        int64_t rowscale_stride, void* out, int dtype, double scale, int nvec, int64_t y_stride,
+                        int64_t out_stride, const void* addw, int64_t addw_stride, const void* addx,
+                        int64_t addx_stride, double* qpart, int64_t qstride, hipStream_t stream) {
+  int st = check_plan(p);
+  if (st != NFT_OK) return st;
+  if (nvec < 1 || nvec > LOS_KMAX || rowscale_stride < 0 || !addw || !addx || addw_stride < 0 || addx_stride < 0 ||
+      (qpart && qstride < nft_los_add_blocks(p))) {
+    set_last_error("nft_los_adjoint_add: 1 <= nvec <= %d, strides >= 0, addw and addx given, "
+                   "qstride >= nft_los_add_blocks", LOS_KMAX);
+    return NFT_ERR_ARG;
+  }
+  if (dtype == 0)
+    return los_adjoint_add_t<double>(p, y, colscale, rowscale, out, scale, nvec, y_stride, out_stride,
+                                     rowscale_stride, addw, addw_stride, addx, addx_stride, qpart, qstride, stream);
+  if (dtype == 1)
+    return los_adjoint_add_t<float>(p, y, colscale, rowscale, out, scale, nvec, y_stride, out_stride,
+                                    rowscale_stride, addw, addw_stride, addx, addx_stride, qpart, qstride, stream);
+  set_last_error("nft_los_adjoint_add: bad dtype %d", dtype);
   return NFT_ERR_ARG;
 }
 

@@ -1045,12 +1045,46 @@ class _CorrelatedFieldModel(Operator):
         lin = x.jac is not None
         v = x.val if lin else x
         lat = {k: v[k].val for k in self._domain.keys()}
+        hit = self._recall(lat)
+        if hit is not None and (not lin or hit[1] is not None):
+            return x.new(hit[0], hit[1]) if lin else hit[0]
         s, a, c, afull = self._value(lat)
         res = Field(self._target, s)
-        if not lin:
-            return res
-        jac = CFJacobian(self, c, a, afull, lat[self.k_xi])
-        return x.new(res, jac)
+        jac = CFJacobian(self, c, a, afull, lat[self.k_xi]) if lin else None
+        if lin:
+            # the value lives as long as its Jacobian (the operators after the
+            # model drop their input's Linearization at once)
+            jac._value = res
+        # the most recent point, by weak references only: its latent tensors
+        # (one per key, with their version counters) and what was made of them
+        self._last = ({k: (weakref.ref(t), t._version) for k, t in lat.items()}, weakref.ref(res),
+                      None if jac is None else weakref.ref(jac))
+        return x.new(res, jac) if lin else res
+
+    def _recall(self, lat):
+        """(value Field, CFJacobian or None) of the last application if it was
+        at these very latent tensors (same objects, not modified since) and its
+        results are still alive, else None.  The branches of a joint
+        likelihood apply the model to one point: they share one evaluation and
+        one Jacobian object, which is how the metric's fusion recognises the
+        shared core."""
+        last = self.__dict__.get("_last")
+        if last is None:
+            return None
+        keys, rres, rjac = last
+        for k, t in lat.items():
+            ref, ver = keys[k]
+            t0 = ref()
+            if t0 is None or t._version != ver:
+                return None
+            if t0 is not t and (t0.data_ptr() != t.data_ptr() or t0.shape != t.shape or t0.stride() != t.stride()
+                                or t0.dtype != t.dtype):
+                return None
+        jac = None if rjac is None else rjac()
+        res = jac._value if jac is not None else rres()
+        if res is None:
+            return None
+        return res, jac
 
     def __repr__(self):
         return f"SimpleCorrelatedField (fused) {self._target.shape}"

@@ -412,6 +412,12 @@ class LOSResponse(LinearOperator):
         middle.supports_fp32 = True
         middle.supports_fold = _FOLD_IN_ADJ
         middle.quad_blocks = int(_native.load().nft_los_quad_blocks(ctypes.byref(plan)))
+        # what the middle is made of, for a caller that fuses it with further
+        # branches (operators/joint_middle.py); read-only
+        middle.response = self
+        middle.plan = plan
+        middle.scales = scales     # dtype -> (pixel-side diagonal, data-side weight) or None each
+        middle.factor = scale
         return middle
 
     @property

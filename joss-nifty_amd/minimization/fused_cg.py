@@ -45,17 +45,28 @@ def fusable_metric(A):
             return None
         return A.fused[0], A.fused[1], 0.0
     if isinstance(A, SumOperator):
-        sand, shift = None, 0.0
+        sands, shift = [], 0.0
         for op, neg in zip(A._ops, A._neg):
-            if isinstance(op, SandwichOperator) and op.fused is not None and not neg and sand is None:
-                sand = op
+            if isinstance(op, SandwichOperator) and op.fused is not None and not neg:
+                sands.append(op)
             elif isinstance(op, ScalingOperator) and complex(op._factor).imag == 0:
                 shift += (-1 if neg else 1) * complex(op._factor).real
             else:
                 return None
-        if sand is None:
+        if not sands:
             return None
-        return sand.fused[0], sand.fused[1], shift
+        if len(sands) == 1:
+            return sands[0].fused[0], sands[0].fused[1], shift
+        # the metric of a joint likelihood (MGVI: lh1.metric + lh2.metric + 1):
+        # sandwiches around one shared model Jacobian add their middles
+        core = sands[0].fused[0]
+        if any(s.fused[0] is not core for s in sands):
+            return None
+        joint = A.__dict__.get("_joint_fused")
+        if joint is None:
+            from ..operators.joint_middle import joint_middle
+            joint = A.__dict__["_joint_fused"] = joint_middle(core, [s.fused[1] for s in sands])
+        return core, joint, shift
     return None
 
 

@@ -1,6 +1,9 @@
 """Energy operators on the sampling path (src/operators/energy_operators.py):
 GaussianEnergy (:478-583), PoissonianEnergy (:586-625), StandardHamiltonian
 (:764-831), the likelihood chain (:152-200) and the quadratic forms."""
+from functools import reduce
+from operator import add
+
 import numpy as np
 
 from .. import utilities
@@ -9,7 +12,7 @@ from ..field import Field
 from ..linearization import Linearization
 from ..multi_domain import MultiDomain
 from ..multi_field import MultiField
-from ..sugar import makeDomain
+from ..sugar import domain_union, makeDomain
 from .adder import Adder
 from .linear_operator import LinearOperator
 from .operator import Operator, _OpChain
@@ -45,6 +48,16 @@ class LikelihoodEnergyOperator(EnergyOperator):
     def __rmatmul__(self, other):
         return _LikelihoodChain(other, self)
 
+    def __add__(self, other):
+        if not isinstance(other, LikelihoodEnergyOperator):
+            return super().__add__(other)
+        return _LikelihoodSum.make([self, other])
+
+    def __radd__(self, other):
+        if not isinstance(other, LikelihoodEnergyOperator):
+            return NotImplemented
+        return _LikelihoodSum.make([other, self])
+
     def get_metric_at(self, x):
         dtp, f = self.get_transformation()
         bun = f(Linearization.make_var(x)).jac
@@ -56,6 +69,8 @@ class LikelihoodEnergyOperator(EnergyOperator):
 
     @name.setter
     def name(self, x):
+        if isinstance(self, _LikelihoodSum):
+            raise RuntimeError("a joint likelihood has no name of its own: name its components")
         self._name = x
 
 
@@ -94,6 +109,115 @@ class _LikelihoodChain(LikelihoodEnergyOperator):
     def apply(self, x):
         self._check_input(x)
         return self._op(x)
+
+
+class _LikelihoodSum(LikelihoodEnergyOperator):
+    """lh1 + lh2 + ...: the joint likelihood of independent data sets
+    (energy_operators.py:208-301).  Every component keeps its own slice of the
+    transformation's target and of the data residuals, keyed by its name
+    (default "Likelihood i"; components with a MultiDomain there contribute
+    their keys prefixed by "name: ")."""
+
+    def __init__(self, ops, _callingfrommake=False):
+        from .simple_linear_operators import PrependKey
+        if not _callingfrommake:
+            raise NotImplementedError
+        if len({isinstance(op.domain, DomainTuple) for op in ops}) != 1:
+            raise RuntimeError("joint likelihood: the components mix DomainTuple and MultiDomain domains")
+        self._ops = tuple(ops)
+        names = self._all_names()
+        if len(set(names)) != len(names):
+            raise ValueError(f"joint likelihood: component names collide: {names}")
+        relabel, residuals, with_data = [], [], []
+        for name, op in zip(names, self._ops):
+            if op._res is None:
+                continue
+            rl = self._relabel(op.data_domain, name, PrependKey)
+            relabel.append(rl)
+            residuals.append(rl @ op._res)
+            with_data.append(op)
+
+        def sqrt_data_metric_at(x):
+            return reduce(add, (rl @ op._sqrt_data_metric_at(x) @ rl.adjoint
+                                for rl, op in zip(relabel, with_data)))
+
+        res = reduce(add, residuals) if residuals else None
+        super().__init__(res, sqrt_data_metric_at if residuals else None)
+        self._domain = domain_union([op.domain for op in self._ops])
+
+    @staticmethod
+    def _relabel(dom, name, PrependKey):
+        """linear map of a component's slice `dom` onto its keys of the joint space"""
+        from .simple_linear_operators import ducktape
+        if isinstance(dom, MultiDomain):
+            return PrependKey(dom, name + ": ")
+        return ducktape(None, dom, name)
+
+    @classmethod
+    def unpack(cls, ops, res):
+        for op in ops:
+            if isinstance(op, cls):
+                res = cls.unpack(op._ops, res)
+            else:
+                res = res + [op]
+        return res
+
+    @classmethod
+    def make(cls, ops):
+        flat = cls.unpack(ops, [])
+        if any(not isinstance(op, LikelihoodEnergyOperator) for op in flat):
+            raise TypeError("joint likelihood: every component must be a LikelihoodEnergyOperator")
+        if len(flat) == 1:
+            return flat[0]
+        return cls(flat, _callingfrommake=True)
+
+    def apply(self, x):
+        self._check_input(x)
+        if x.jac is None:
+            return reduce(add, (op.force(x) for op in self._ops))
+        lin = [op(Linearization.make_var(x.val.extract(op.domain), x.want_metric)) for op in self._ops]
+        jac = reduce(lambda a, b: a._myadd(b, False), (ll.jac for ll in lin))
+        res = x.new(reduce(add, (ll.val for ll in lin)), jac)
+        metrics = [ll.metric for ll in lin]
+        if all(mm is not None for mm in metrics):
+            res = res.add_metric(reduce(add, metrics))
+        return res
+
+    def get_transformation(self):
+        from .simple_linear_operators import PrependKey
+        trs = [op.get_transformation() for op in self._ops]
+        if any(tr is None for tr in trs):
+            return None
+        dtype, parts = {}, []
+        for name, (dtp, tr) in zip(self._all_names(), trs):
+            if isinstance(tr.target, MultiDomain):
+                pre = name + ": "
+                for k in tr.target.keys():
+                    dtype[pre + k] = dtp[k] if isinstance(dtp, dict) else dtp
+                parts.append(PrependKey(tr.target, pre) @ tr)
+            else:
+                dtype[name] = dtp
+                parts.append(tr.ducktape_left(name))
+        return dtype, reduce(add, parts)
+
+    def _get_name(self, i):
+        name = self._ops[i].name
+        return f"Likelihood {i}" if name is None else name
+
+    def _all_names(self):
+        return [self._get_name(i) for i in range(len(self._ops))]
+
+    def _simplify_for_constant_input_nontrivial(self, c_inp):
+        # the constants are inserted once in front of the whole sum, so the
+        # components still see one shared point (and share its model evaluation)
+        from .simplify_for_const import InsertionOperator
+        return None, self @ InsertionOperator(self.domain, c_inp)
+
+    def __repr__(self):
+        subs = []
+        for name, op in zip(self._all_names(), self._ops):
+            subs += [f"*{name}*", repr(op)]
+        return "_LikelihoodSum:\n" + utilities.indent("\n".join(subs))
 
 
 class Squared2NormOperator(EnergyOperator):

@@ -6,7 +6,11 @@ library/correlated_fields_simple.py) and every other factor is pointwise on
 J's target grid (diagonal, scaling, geometry removal), the whole sandwich
 J^T W J with W = cheese * prod D_i^2 is evaluated by J's fused native
 pipeline (J.sandwich_apply) instead of operator by operator.  Results are the
-same linear map; only the number of HBM passes changes."""
+same linear map; only the number of HBM passes changes.
+
+A bun that is a SUM of such chains onto distinct keys of a MultiDomain (the
+transformation of a joint likelihood, lh1 + lh2) around ONE J fuses the same
+way, with the sum of the branches' middles (operators/joint_middle.py)."""
 import torch
 
 from .. import utilities
@@ -96,6 +100,85 @@ def _fused_response_middle(left, cheese, fct):
     return R.fused_middle(dr, c, fct)
 
 
+def _chain_fusion(ops, cheese0):
+    """(core, middle) for a bun  D_k ... D_1 J  given as its factor list `ops`
+    (outermost first) and the cheese, or None (see the module docstring)."""
+    cores = [i for i, op in enumerate(ops) if hasattr(op, "sandwich_apply")]
+    if len(cores) != 1:
+        return None
+    core = ops[cores[0]]
+    # factors applied before the core (right of it) may only be scalars
+    # (ChainOperator.simplify moves folded scalars to the end of the chain)
+    right = ops[cores[0] + 1:]
+    if not all(isinstance(op, ScalingOperator) for op in right):
+        return None
+    w = _pointwise_weight(ops[:cores[0]] + right, cheese0)
+    if w is None:
+        # non-pointwise middle (e.g. a line-of-sight response): the model
+        # Jacobian halves stay fused, the middle M^T C M runs through the
+        # generic operator tree on J's target
+        if not all(isinstance(op, ScalingOperator) and complex(op._factor).imag == 0 for op in right):
+            return None
+        fct = 1.
+        for op in right:
+            fct *= complex(op._factor).real ** 2
+        left = ops[:cores[0]]
+        fm = _fused_response_middle(left, cheese0, fct)
+        if fm is not None:
+            return core, fm
+        mid = ChainOperator.make(left) if len(left) > 0 else None
+        cheese = cheese0
+        tgt = core.target
+
+        def middle(s):
+            from ..field import Field
+            f = Field(tgt, s)
+            if mid is None:
+                r = cheese(f)
+            else:
+                r = mid.adjoint_times(cheese(mid(f)))
+            return r.val * fct if fct != 1. else r.val
+        return core, middle
+    if not torch.is_tensor(w):
+        w = torch.full(core.target.shape, float(w), dtype=torch.float64, device=core.device)
+    else:
+        w = w.expand(core.target.shape).contiguous()
+    return core, w
+
+
+def _sum_fusion(bun, cheese):
+    """(core, joint middle) for the bun of a joint likelihood (geoVI:
+    Sandwich(fl.jac, scale)): a sum of chains  [adapter onto a key of its own,
+    pointwise / response factors..., core, scalars...]  that all end in the
+    SAME fused Jacobian, under a real scaling as cheese.  The keys are
+    distinct, so no cross terms arise and the middles add (joint_middle)."""
+    from .joint_middle import joint_middle
+    from .simple_linear_operators import FieldAdapter
+    from ..multi_domain import MultiDomain
+    if not isinstance(cheese, ScalingOperator) or complex(cheese._factor).imag != 0:
+        return None
+    fct = complex(cheese._factor).real
+    core, parts, keys = None, [], set()
+    for term in bun._ops:
+        ops = list(term._ops) if isinstance(term, ChainOperator) else [term]
+        ad = ops[0]
+        if not (isinstance(ad, FieldAdapter) and isinstance(ad.target, MultiDomain) and len(ad.target) == 1
+                and len(ops) > 1):
+            return None
+        key = ad.target.keys()[0]
+        if key in keys:
+            return None
+        keys.add(key)
+        f = _chain_fusion(ops[1:], ScalingOperator(ad.domain, fct))
+        if f is None or (core is not None and f[0] is not core):
+            return None
+        core = f[0]
+        parts.append(f[1])
+    if core is None:
+        return None
+    return core, joint_middle(core, parts)
+
+
 class SandwichOperator(EndomorphicOperator):
     def __init__(self, bun, cheese, op, _callingfrommake=False):
         if not _callingfrommake:
@@ -109,51 +192,13 @@ class SandwichOperator(EndomorphicOperator):
         self._detect_fusion()
 
     def _detect_fusion(self):
+        from .sum_operator import SumOperator
         bun = self._bun
+        if isinstance(bun, SumOperator):
+            self._fused = _sum_fusion(bun, self._cheese)
+            return
         ops = list(bun._ops) if isinstance(bun, ChainOperator) else [bun]
-        cores = [i for i, op in enumerate(ops) if hasattr(op, "sandwich_apply")]
-        if len(cores) != 1:
-            return
-        core = ops[cores[0]]
-        # factors applied before the core (right of it) may only be scalars
-        # (ChainOperator.simplify moves folded scalars to the end of the chain)
-        right = ops[cores[0] + 1:]
-        if not all(isinstance(op, ScalingOperator) for op in right):
-            return
-        w = _pointwise_weight(ops[:cores[0]] + right, self._cheese)
-        if w is None:
-            # non-pointwise middle (e.g. a line-of-sight response): the model
-            # Jacobian halves stay fused, the middle M^T C M runs through the
-            # generic operator tree on J's target
-            if not all(isinstance(op, ScalingOperator) and complex(op._factor).imag == 0 for op in right):
-                return
-            fct = 1.
-            for op in right:
-                fct *= complex(op._factor).real ** 2
-            left = ops[:cores[0]]
-            fm = _fused_response_middle(left, self._cheese, fct)
-            if fm is not None:
-                self._fused = (core, fm)
-                return
-            mid = ChainOperator.make(left) if len(left) > 0 else None
-            cheese = self._cheese
-            tgt = core.target
-
-            def middle(s):
-                from ..field import Field
-                f = Field(tgt, s)
-                if mid is None:
-                    r = cheese(f)
-                else:
-                    r = mid.adjoint_times(cheese(mid(f)))
-                return r.val * fct if fct != 1. else r.val
-            self._fused = (core, middle)
-            return
-        if not torch.is_tensor(w):
-            w = torch.full(core.target.shape, float(w), dtype=torch.float64, device=core.device)
-        else:
-            w = w.expand(core.target.shape).contiguous()
-        self._fused = (core, w)
+        self._fused = _chain_fusion(ops, self._cheese)
 
     @staticmethod
     def make(bun, cheese=None, sampling_dtype=None):

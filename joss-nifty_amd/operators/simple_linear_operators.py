@@ -170,3 +170,26 @@ class PartialExtractor(LinearOperator):
         res0 = MultiField.from_dict({key: x[key] for key in x.domain.keys()})
         res1 = MultiField.full(self._compldomain, 0.)
         return res0.unite(res1)
+
+
+class PrependKey(LinearOperator):
+    """Relabel a MultiDomain: every key k becomes pre + k, values untouched
+    (simple_linear_operators.py:437-461)."""
+
+    def __init__(self, domain, pre):
+        from ..sugar import makeDomain
+        if not isinstance(domain, MultiDomain):
+            raise ValueError("PrependKey needs a MultiDomain")
+        self._domain = makeDomain(domain)
+        self._pre = str(pre)
+        self._target = MultiDomain.make({self._pre + k: d for k, d in self._domain.items()})
+        self._capability = self.TIMES | self.ADJOINT_TIMES
+
+    def apply(self, x, mode):
+        self._check_input(x, mode)
+        if mode == self.TIMES:
+            return MultiField.from_dict({self._pre + k: x[k] for k in self._domain.keys()}, domain=self._target)
+        return MultiField.from_dict({k: x[self._pre + k] for k in self._domain.keys()}, domain=self._domain)
+
+    def __repr__(self):
+        return f"PrependKey '{self._pre}'"
