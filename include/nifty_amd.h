@@ -38,6 +38,9 @@
  *                      matrix, src/library/los_response.py:180-233
  *   nft_spmv_*         LOSResponse.apply (scipy COO matvec / rmatvec),
  *                      src/library/los_response.py:226-233
+ *   nft_samp_*         MaskOperator.apply, src/operators/mask_operator.py:50-59, and
+ *                      LinearInterpolator.apply (scipy COO matvec / rmatvec of
+ *                      _build_mat), src/operators/linear_interpolation.py:69-103
  */
 #ifndef NIFTY_AMD_H
 #define NIFTY_AMD_H
@@ -470,6 +473,64 @@ int nft_los_adjoint_add(const nft_los_plan* plan, const void* y, const void* col
                         double scale, int nvec, int64_t y_stride, int64_t out_stride,
                         const void* addw, int64_t addw_stride, const void* addx,
                         int64_t addx_stride, double* qpart, int64_t qstride, hipStream_t stream);
+
+/* ---- sampling responses (mask, multilinear interpolation) -------------- */
+/* MaskOperator (src/operators/mask_operator.py) and LinearInterpolator
+ * (src/operators/linear_interpolation.py): every data point reads ncorner = 1
+ * (mask) or 2^ndim (interpolation) grid values.  No weights are stored: the
+ * kernels recompute
+ *   w_{p,c} = prod over axes d of (bit_d(c) ? frac[d][p] : 1 - frac[d][p])
+ * in fp64, multiplied in axis order, bit_d(c) = (c >> (ndim-1-d)) & 1 (the
+ * first axis is the slowest bit: np.mgrid ravel order) -- bitwise the
+ * reference's _build_mat.  Corner c of point p reads the pixel whose index
+ * along axis d is idx[d][p] + bit_d(c), wrapped to 0 at shape[d] (periodic).
+ * The plan may list the points in any order (the host sorts them by pixel
+ * tile, so that neighbouring lanes gather from neighbouring grid lines):
+ * position s of the plan holds datum point[s].
+ *   point    [npoints] int32, a permutation; NULL: the identity
+ *   idx      [ndim][npoints] int32 by position, each in [0, shape[d])
+ *   frac     [ndim][npoints] fp64 by position, in [0, 1]; NULL for a mask,
+ *            whose grid is viewed flat (ndim = 1, shape[0] = npix, idx = the
+ *            kept pixel)
+ *   pix_ptr  [npix + 1] int32: the entries of grid pixel j are
+ *            ent[pix_ptr[j] .. pix_ptr[j+1])
+ *   ent      [npoints * ncorner] int32: position * ncorner + corner, sorted by
+ *            (pixel, corner, datum) -- per pixel the reference's COO order.
+ * Any number of entries may share a pixel.  With npoints = 0 the arrays may
+ * be NULL: the forward writes nothing, the adjoint stores zeros. */
+typedef struct nft_samp_plan {
+  int64_t npoints, npix;
+  int ndim, ncorner;
+  int64_t shape[3];
+  const int* point;
+  const int* idx;
+  const double* frac;
+  const int* pix_ptr;
+  const int* ent;
+} nft_samp_plan;
+
+/* y[v, p] = scale * rowscale[p] * sum_c w_{p,c} * (colscale_v[j] * x[v, j]),
+ * j the pixel of corner c, summed in corner order in fp64; colscale_v =
+ * colscale + v * colscale_stride (0: one shared pixel factor, as
+ * nft_los_forward_ex).  1 <= nvec <= 8; per vector the result is bitwise
+ * independent of nvec.  qpart (NULL: none): qpart[v * qstride + b] = the sum
+ * over the points at positions [256 b, 256 b + 256) of t_p * y_p (t the sum before scale * rowscale,
+ * y the stored output) in a fixed order independent of nvec, b <
+ * nft_samp_quad_blocks(plan).  dtype as nft_los_*: storage fp64 (0) or fp32
+ * (1), accumulation always fp64. */
+int nft_samp_quad_blocks(const nft_samp_plan* plan);
+int nft_samp_forward_batched(const nft_samp_plan* plan, const void* x, const void* colscale,
+                             int64_t colscale_stride, const void* rowscale, void* y, int dtype,
+                             double scale, int nvec, int64_t x_stride, int64_t y_stride,
+                             double* qpart, int64_t qstride, hipStream_t stream);
+/* out[v, j] = scale * rowscale_v[j] * sum_{(c,p) -> j} w_{p,c} * (colscale[p] * y[v, p])
+ * per pixel in ascending (corner, point) order in fp64; rowscale_v = rowscale
+ * + v * rowscale_stride (0: shared).  EVERY grid pixel is stored by the one
+ * launch, pixels without entries as 0; no atomics: bitwise reproducible. */
+int nft_samp_adjoint_batched(const nft_samp_plan* plan, const void* y, const void* colscale,
+                             const void* rowscale, int64_t rowscale_stride, void* out, int dtype,
+                             double scale, int nvec, int64_t y_stride, int64_t out_stride,
+                             hipStream_t stream);
 
 /* ---- curvature from the data space ------------------------------------ */
 /* For a CG metric shift * 1 + J^T R^T C R J (the LOS sampling metric) the

@@ -46,7 +46,9 @@ from .operators.energy_operators import (EnergyOperator, GaussianEnergy, Likelih
                                          StandardHamiltonian)
 from .operators.harmonic_operators import (FFTOperator, HarmonicSmoothingOperator, HarmonicTransformOperator,
                                            HartleyOperator)
+from .operators.linear_interpolation import LinearInterpolator
 from .operators.linear_operator import LinearOperator
+from .operators.mask_operator import MaskOperator
 from .operators.normal_operators import LognormalTransform, NormalTransform
 from .operators.operator import Operator
 from .operators.operator_adapter import OperatorAdapter

@@ -65,6 +65,9 @@ SIGNATURES = {
     "nft_los_add_blocks": (_i, [_p]),
     "nft_los_adjoint_add": (_i, [_p, _p, _p, _p, _i64, _p, _i, _d, _i, _i64, _i64, _p, _i64, _p, _i64, _p, _i64,
                                  _p]),
+    "nft_samp_quad_blocks": (_i, [_p]),
+    "nft_samp_forward_batched": (_i, [_p, _p, _p, _i64, _p, _p, _i, _d, _i, _i64, _i64, _p, _i64, _p]),
+    "nft_samp_adjoint_batched": (_i, [_p, _p, _p, _p, _i64, _p, _i, _d, _i, _i64, _i64, _p]),
     "nft_cg_dd_blocks": (_i, [_i64]),
     "nft_cg_direction_dd_batched": (_i, [_p, _p, _i64, _i64, _i, _i, _p, _d, _p, _i64, _p]),
     "nft_fold_partials": (_i, [_p, _i, _i, _p, _i64, _p]),
@@ -124,6 +127,12 @@ class LosPlan(ctypes.Structure):
                [(n, _p) for n in ("item_box", "item_seg", "item_ent", "seg_ent", "seg_slot", "ent_loc", "ent_wf",
                                   "los_ptr", "box_ent", "pix_off", "box_lptr", "box_lines", "ent_lidx")] + \
                [("lidx8", _i), ("ent_wa", _p), ("box_item", _p), ("box_ent_adj", _p)]
+
+
+class SampPlan(ctypes.Structure):
+    """nft_samp_plan (include/nifty_amd.h)."""
+    _fields_ = [("npoints", _i64), ("npix", _i64), ("ndim", _i), ("ncorner", _i), ("shape", _i64 * 3)] + \
+               [(n, _p) for n in ("point", "idx", "frac", "pix_ptr", "ent")]
 
 
 class AmpConst(ctypes.Structure):
@@ -685,6 +694,48 @@ def los_adjoint_add(plan, y, out, addw, addx, colscale=None, rowscale=None, scal
     _check(lib.nft_los_adjoint_add(ctypes.byref(plan), ptr(y), ptr(colscale), ptr(rowscale), rss, ptr(out),
                                    dtype_code(y.dtype), float(scale), k, y[0].numel(), npix, ptr(addw), aws,
                                    ptr(addx), npix, ptr(qpart), qs, stream_ptr()))
+    return out
+
+
+SAMP_KMAX = 8      # vectors per batched sampling launch (csrc/nft_samp.hip)
+
+
+def samp_quad_blocks(plan):
+    return int(load().nft_samp_quad_blocks(ctypes.byref(plan)))
+
+
+def samp_forward(plan, x, y, colscale=None, rowscale=None, scale=1.0, qpart=None):
+    """y[b] = scale * rowscale * R (colscale[b] * x[b]) on a sampling plan
+    (SampPlan; x: (k, npix), y: (k, npoints), k <= 8, contiguous): colscale
+    one shared pixel vector or one per vector; qpart (k, >=
+    nft_samp_quad_blocks) fp64 rows or None (nft_samp_forward_batched)."""
+    lib = load()
+    require_device(x, y, colscale, rowscale)
+    k = x.shape[0]
+    css = _pixel_scale_stride(colscale, k, x[0].numel())
+    qs = 0
+    if qpart is not None:
+        if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1
+                and qpart.shape[0] >= k):
+            raise NativeError("qpart: (k, >= nft_samp_quad_blocks) fp64 device rows with unit element stride")
+        qs = qpart.stride(0)
+    _check(lib.nft_samp_forward_batched(ctypes.byref(plan), ptr(x), ptr(colscale), css, ptr(rowscale), ptr(y),
+                                        dtype_code(x.dtype), float(scale), k, x[0].numel(), y[0].numel(),
+                                        ptr(qpart), qs, stream_ptr()))
+    return y
+
+
+def samp_adjoint(plan, y, out, colscale=None, rowscale=None, scale=1.0):
+    """out[b] = scale * rowscale[b] * R^T (colscale * y[b]): every pixel of
+    out is written; the pixel-side rowscale one shared vector or one per
+    vector (nft_samp_adjoint_batched)."""
+    lib = load()
+    require_device(y, out, colscale, rowscale)
+    k = y.shape[0]
+    rss = _pixel_scale_stride(rowscale, k, out[0].numel())
+    _check(lib.nft_samp_adjoint_batched(ctypes.byref(plan), ptr(y), ptr(colscale), ptr(rowscale), rss, ptr(out),
+                                        dtype_code(y.dtype), float(scale), k, y[0].numel(), out[0].numel(),
+                                        stream_ptr()))
     return out
 
 

@@ -13,7 +13,8 @@ per expansion point into a composition of native calls on raw device tensors:
   * grid / data fields are plain tensors,
   * the correlated-field Jacobian (CFJacobian) runs its fused transforms,
   * runs of pointwise factors around a LOSResponse are folded into the LOS
-    kernels' column / row scales (nft_los_*),
+    kernels' column / row scales (nft_los_*); likewise around a MaskOperator
+    or LinearInterpolator (nft_samp_*),
   * a sum "alpha * 1 + X" whose X ends in a CF Jacobian adjoint is folded
     into that adjoint's epilogue (out = alpha * x + X x).
 
@@ -72,6 +73,7 @@ def _adj_parts(op, adjoint):
 def _lower_leaf(op, adjoint):
     from .library.correlated_fields_simple import CFJacobian
     from .library.los_response import LOSResponse
+    from .operators.sampling_plan import SamplingResponse
     op, adjoint = _adj_parts(op, adjoint)
     if _is_real_scale(op) and isinstance(op.domain, MultiDomain):
         v = complex(op._factor).real  # packed latent buffers: padding stays zero
@@ -103,6 +105,8 @@ def _lower_leaf(op, adjoint):
         return f
     if isinstance(op, LOSResponse):
         return _los(op, adjoint, None, None, 1.0)
+    if isinstance(op, SamplingResponse):
+        return _samp(op, adjoint, None, None, 1.0)
     raise _Unsupported(op)
 
 
@@ -128,6 +132,24 @@ def _los(R, adjoint, cin, cout, scale):
     return f
 
 
+def _samp(R, adjoint, cin, cout, scale):
+    """A sampling response (MaskOperator, LinearInterpolator) or its adjoint
+    with the pointwise factors cin / cout and `scale` folded into the nft_samp
+    launch, as _los; the adjoint writes every pixel (zeros where no datum
+    lands)."""
+    gshape = R.domain.shape
+    cin = None if cin is None else cin.reshape(-1).contiguous()
+    cout = None if cout is None else cout.reshape(-1).contiguous()
+    if not adjoint:
+        def f(x, acc=None, alpha=0.):
+            return _finish(R._fwd(x.reshape(1, -1), colscale=cin, rowscale=cout, scale=scale)[0], acc, alpha)
+    else:
+        def f(x, acc=None, alpha=0.):
+            out = R._adj(x.reshape(1, -1), colscale=cin, rowscale=cout, scale=scale)
+            return _finish(out.reshape(gshape), acc, alpha)
+    return f
+
+
 def _fold(items):
     """product of pointwise items -> (tensor or None, float scale)"""
     t, s = None, 1.0
@@ -142,6 +164,7 @@ def _fold(items):
 def _lower_chain(ops, adjoint):
     """ops: chain factors outermost first.  Returns a callable."""
     from .library.los_response import LOSResponse
+    from .operators.sampling_plan import SamplingResponse
     seq = [(_adj_parts(op, adjoint)) for op in (reversed(ops) if adjoint else ops)]
     # application order: innermost first
     seq = list(reversed(seq))
@@ -149,7 +172,7 @@ def _lower_chain(ops, adjoint):
     i = 0
     while i < len(seq):
         op, adj = seq[i]
-        if isinstance(op, LOSResponse):
+        if isinstance(op, (LOSResponse, SamplingResponse)):
             # absorb the pointwise run before (input side) and after (output side)
             pre = []
             while fns and fns[-1][0] == "pw":
@@ -161,7 +184,8 @@ def _lower_chain(ops, adjoint):
                 j += 1
             cin, s_in = _fold(pre)
             cout, s_out = _fold(post)
-            fns.append(("fn", _los(op, adj, cin, cout, s_in * s_out)))
+            lower_r = _los if isinstance(op, LOSResponse) else _samp
+            fns.append(("fn", lower_r(op, adj, cin, cout, s_in * s_out)))
             i = j
             continue
         pw = _pointwise(op)

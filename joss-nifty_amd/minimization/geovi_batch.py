@@ -254,7 +254,8 @@ class _PtwStage:
 
 
 class _LinStage:
-    """linear stage without state: ('scale', s) | ('diag', t) | ('reshape',) | ('los', R)"""
+    """linear stage without state: ('scale', s) | ('diag', t) | ('reshape',) | ('los', R) |
+    ('samp', R: MaskOperator / LinearInterpolator)"""
 
     def __init__(self, kind, v, dom_shape, tgt_shape):
         self.kind, self.v = kind, v
@@ -275,6 +276,8 @@ class _LinStage:
             return (V.reshape((k,) + self.dshape) * self.v).reshape((k,) + self.tshape)
         if self.kind == "reshape":
             return V.reshape((k,) + self.tshape)
+        if self.kind == "samp":
+            return self.v._fwd(V.reshape(k, -1))
         return _los_fwd(self.v, V.reshape(k, -1))
 
     def vjp(self, _, G):
@@ -285,6 +288,8 @@ class _LinStage:
             return (G.reshape((k,) + self.tshape) * self.v).reshape((k,) + self.dshape)
         if self.kind == "reshape":
             return G.reshape((k,) + self.dshape)
+        if self.kind == "samp":
+            return self.v._adj(G.reshape(k, -1)).reshape((k,) + self.dshape)
         return _los_adj(self.v, G.reshape(k, -1)).reshape((k,) + self.dshape)
 
 
@@ -346,6 +351,7 @@ class Pipeline:
         from ..library.los_response import LOSResponse
         from ..operators.diagonal_operator import DiagonalOperator
         from ..operators.operator import _FunctionApplier, _OpChain
+        from ..operators.sampling_plan import SamplingResponse
         from ..operators.scaling_operator import ScalingOperator
         from ..operators.simple_linear_operators import GeometryRemover
         from ..pointwise import ptw_dict
@@ -366,6 +372,9 @@ class Pipeline:
                 stages.append(_LinStage("reshape", None, op.domain.shape, op.target.shape))
             elif isinstance(op, LOSResponse):
                 stages.append(_LinStage("los", op, op.domain.shape, op.target.shape))
+            elif isinstance(op, SamplingResponse):
+                # MaskOperator / LinearInterpolator: plain batched launches
+                stages.append(_LinStage("samp", op, op.domain.shape, op.target.shape))
             elif isinstance(op, _FunctionApplier) and op._funcname in ptw_dict:
                 stages.append(_PtwStage(op._funcname, op._args, op._kwargs))
             else:
