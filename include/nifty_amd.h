@@ -339,7 +339,8 @@ typedef struct nft_hartley_fuse {
    * workgroups of the R2C row pass (any other geometry, or with a prologue:
    * by nft_fold_partials launched first).  It lets the adjoint transform of
    * a sampling metric with a pointwise W fold the quad_part partials of the
-   * forward one on its way (conjugate_gradient.py:101's d.q). */
+   * forward one on its way (conjugate_gradient.py:101's d.q).  fold_ostride
+   * >= 1 (NFT_ERR_ARG otherwise, as nft_los_adjoint_fold). */
   const double* fold_part;
   int64_t fold_nb;
   double* fold_out;
@@ -571,7 +572,10 @@ int nft_cg_lazy_flush(void* x, void* d, const void* ring, int64_t sstride, const
  * fold_nrhs, fold_out, fold_ostride) in ONE launch (the fold runs as the first
  * fold_nrhs workgroups of the adjoint's grid, bitwise the separate call): the
  * carried CG's curvature, needed only by the adjoint transform's last pass,
- * without a launch of its own between the two LOS passes and the transform. */
+ * without a launch of its own between the two LOS passes and the transform.
+ * fold_ostride >= 1.  A plan without boxes has no adjoint launch: the fold
+ * runs as nft_fold_partials on its own (NFT_OK, `out` not written, as
+ * nft_los_adjoint_batched). */
 int nft_los_adjoint_fold(const nft_los_plan* plan, const void* y, const void* colscale,
                          const void* rowscale, void* out, int dtype, double scale, int nvec,
                          int64_t y_stride, int64_t out_stride, const double* fold_part, int fold_nb,

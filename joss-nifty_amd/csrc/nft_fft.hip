@@ -1533,9 +1533,9 @@ int nft_hartley_fused(const nft_hartley_fuse* fz, const void* in, void* out, int
     f.fnrhs = 0;
     if (fz->fold_nrhs > 0) {
       if (!fz->fold_part || !fz->fold_out || fz->fold_nb < 1 || fz->fold_nb > 0x7fffffffLL ||
-          fz->fold_nrhs > 65535) {
-        set_last_error("nft_hartley_fused: the carried fold needs its partials, output, 1 <= fold_nb and "
-                       "fold_nrhs <= 65535");
+          fz->fold_nrhs > 65535 || fz->fold_ostride < 1) {
+        set_last_error("nft_hartley_fused: the carried fold needs its partials, output, 1 <= fold_nb, "
+                       "fold_nrhs <= 65535 and fold_ostride >= 1");
         return NFT_ERR_ARG;
       }
       f.fpart = fz->fold_part;

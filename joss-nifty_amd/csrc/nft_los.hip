@@ -880,11 +880,17 @@ int nft_los_adjoint_fold(const nft_los_plan* p, const void* y, const void* colsc
                          hipStream_t stream) {
   int st = check_plan(p);
   if (st != NFT_OK) return st;
-  if (nvec < 1 || nvec > LOS_KMAX || p->nbox <= 0 || !fold_part || !fold_out || fold_nb < 1 || fold_nrhs < 1 ||
-      fold_ostride < 1) {
-    set_last_error("nft_los_adjoint_fold: 1 <= nvec <= %d, a non-empty plan and fold partials / output", LOS_KMAX);
+  if (nvec < 1 || nvec > LOS_KMAX || !fold_part || !fold_out || fold_nb < 1 || fold_nrhs < 1 || fold_ostride < 1) {
+    set_last_error("nft_los_adjoint_fold: 1 <= nvec <= %d and fold partials / output", LOS_KMAX);
     return NFT_ERR_ARG;
   }
+  if (dtype != 0 && dtype != 1) {
+    set_last_error("nft_los_adjoint_fold: bad dtype %d", dtype);
+    return NFT_ERR_ARG;
+  }
+  // a plan without boxes has no pixels (nft_los_adjoint_batched: NFT_OK,
+  // nothing written): no launch to carry the fold, so it runs on its own
+  if (p->nbox <= 0) return nft_fold_partials(fold_part, fold_nb, fold_nrhs, fold_out, fold_ostride, stream);
   const LosFold f{fold_part, fold_out, (long long)fold_ostride, fold_nb, fold_nrhs};
   if (dtype == 0)
     return los_adjoint_t<double>(p, y, colscale, rowscale, out, scale, nvec, y_stride, out_stride, stream, 0, &f);

@@ -20,8 +20,11 @@
 // mixes the rounding of its two packed rows); per item the result does not
 // depend on the batch (single == batched, compaction bitwise).
 // d.d partials: thread t sums positions t, t + NT, ... of row g, then those
-// of row n0 - g (pro_rows_kernel's order at NT = 256), the waves folded in
-// order, one slot per mirror row group (nft_hartley_dir_blocks).
+// of row n0 - g, the waves folded in order, one slot per mirror row group
+// (nft_hartley_dir_blocks).  With NT = N / 8 threads that is the summation
+// order of pro_rows_kernel (256 threads) only for rows of N = 2048; for the
+// other row lengths the partials differ from the split path's in the last
+// bits.
 #include <cstdlib>
 
 #include "fast_dispatch.hpp"

@@ -154,8 +154,10 @@ def test_lazy_iterate_bitwise(ift, which, monkeypatch):
     per-step update -- across the residual refreshes and a compaction"""
     from nifty_amd import _native
     from nifty_amd.minimization import fused_cg
-    # these small 2-D grids take the fused prologue + R2C pass, which keeps
-    # its direction in place: the row-staged prologue here
+    # NFT_PRO_R2C=0 selects the row-staged prologue (pro_rows_kernel), the one
+    # that writes the directions to the ring slots; the fused prologue + R2C
+    # pass serves rows of 512 and longer only, so these small grids take the
+    # row-staged one with or without the setting
     monkeypatch.setenv("NFT_PRO_R2C", "0")
     cf, A, (core, W, shift) = _metric(ift, which)
     es = _energies(ift, cf, A, 4, 9)
