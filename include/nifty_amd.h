@@ -41,6 +41,9 @@
  *   nft_samp_*         MaskOperator.apply, src/operators/mask_operator.py:50-59, and
  *                      LinearInterpolator.apply (scipy COO matvec / rmatvec of
  *                      _build_mat), src/operators/linear_interpolation.py:69-103
+ *   nft_lh_*           BernoulliEnergy / StudentTEnergy / InverseGammaEnergy value,
+ *                      gradient, Fisher weight and Bernoulli's transformation,
+ *                      src/operators/energy_operators.py:628-761
  */
 #ifndef NIFTY_AMD_H
 #define NIFTY_AMD_H
@@ -107,6 +110,36 @@ int nft_scale(void* x, int64_t n, int dtype, double scale, hipStream_t stream);
  * fp64, 1 fp32): the value and derivative of the `sigmoid` pointwise map
  * (src/pointwise.py) in one pass, bitwise the separate elementwise passes. */
 int nft_sigmoid_pair(const void* x, void* v, void* d, int64_t n, int dtype, hipStream_t stream);
+
+/* ---- pointwise likelihoods ------------------------------------------- */
+#define NFT_LH_BERNOULLI 0
+#define NFT_LH_STUDENT_T 1
+#define NFT_LH_INVGAMMA 2
+/* Value and derivative of a likelihood's whitening transformation in one pass
+ * over n values (dtype 0 fp64, 1 fp32 storage; fp64 arithmetic).  kind
+ * NFT_LH_BERNOULLI (the only one that is not a chain of existing maps):
+ * t = -2 atan(sqrt((1 - f) / f)), dt = 1 / sqrt(f (1 - f)).  Arguments are
+ * validated as by nft_sigmoid_pair; n == 0 is a no-op. */
+int nft_lh_transform_pair(int kind, const void* f, void* t, void* dt, int64_t n, int dtype,
+                          hipStream_t stream);
+/* Energy, gradient and Fisher weight of a pointwise likelihood for nrhs rows
+ * of model output f (n values each, rows vstride >= n elements apart, dtype
+ * 0 fp64 / 1 fp32).  p0, p1: fp64 parameter arrays of length n shared by the
+ * rows, c0 a scalar; `scale` (the factor of lh.scale) multiplies all outputs.
+ *   kind        parameters            E (summed over the row)             dE/df                 W
+ *   BERNOULLI   p0 = d (0.0 / 1.0)    -log(f) d + log(1 - f) (d - 1)      -d/f + (1-d)/(1-f)    1/(f (1-f))
+ *   STUDENT_T   p0 = theta, or NULL   (theta+1)/2 log1p(f^2/theta)        (theta+1) f/(theta+f^2)  (theta+1)/(theta+3)
+ *               and c0 = theta
+ *   INVGAMMA    p0 = alpha+1,         (alpha+1) log(f) + beta/f           (alpha+1)/f - beta/f^2   (alpha+1)/f^2
+ *               p1 = beta
+ * Outputs, each skipped when NULL: value[row] (fp64), grad and weight (storage
+ * dtype, rows vstride apart; elements between n and vstride are not touched).
+ * All arithmetic and the sums are fp64.  value is a two-level reduction like
+ * nft_dot_batched (ws: nrhs times nft_reduce_workspace(n), needed only with
+ * value); row i of a batched call is bitwise the nrhs = 1 call on that row. */
+int nft_lh_eval_batched(int kind, const void* f, const double* p0, const double* p1, double c0, int64_t n,
+                        int64_t vstride, int nrhs, int dtype, double scale, double* value, void* grad,
+                        void* weight, void* ws, hipStream_t stream);
 /* For the metric shift*1 + M' with q = M' d formed without the shift:
  * sc[CURV] = sum d*(q + shift*d) */
 int nft_cg_curv(const void* d, const void* q, int64_t n, int dtype, double shift, double* sc,

@@ -41,9 +41,9 @@ from .operators.contraction_operator import ContractionOperator, IntegrationOper
 from .operators.diagonal_operator import DiagonalOperator
 from .operators.distributors import DOFDistributor, PowerDistributor
 from .operators.endomorphic_operator import EndomorphicOperator
-from .operators.energy_operators import (EnergyOperator, GaussianEnergy, LikelihoodEnergyOperator,
-                                         PoissonianEnergy, QuadraticFormOperator, Squared2NormOperator,
-                                         StandardHamiltonian)
+from .operators.energy_operators import (BernoulliEnergy, EnergyOperator, GaussianEnergy, InverseGammaEnergy,
+                                         LikelihoodEnergyOperator, PoissonianEnergy, QuadraticFormOperator,
+                                         Squared2NormOperator, StandardHamiltonian, StudentTEnergy)
 from .operators.harmonic_operators import (FFTOperator, HarmonicSmoothingOperator, HarmonicTransformOperator,
                                            HartleyOperator)
 from .operators.linear_interpolation import LinearInterpolator
@@ -58,6 +58,7 @@ from .operators.scaling_operator import ScalingOperator
 from .operators.simple_linear_operators import (ConjugationOperator, FieldAdapter, GeometryRemover,
                                                 NullOperator, PartialExtractor, PrependKey, Realizer,
                                                 VdotOperator, ducktape)
+from .operators.simplify_for_const import ConstantOperator
 from .operators.sum_operator import SumOperator
 from .operators.value_inserter import ValueInserter
 from .sugar import (domain_union, exp, from_random, full, is_fieldlike, is_linearization, is_operator, log,

@@ -28,6 +28,8 @@ SIGNATURES = {
     "nft_dot": (_i, [_p, _p, _i64, _i, _p, _p, _p]),
     "nft_scale": (_i, [_p, _i64, _i, _d, _p]),
     "nft_sigmoid_pair": (_i, [_p, _p, _p, _i64, _i, _p]),
+    "nft_lh_transform_pair": (_i, [_i, _p, _p, _p, _i64, _i, _p]),
+    "nft_lh_eval_batched": (_i, [_i, _p, _p, _p, _d, _i64, _i64, _i, _i, _d, _p, _p, _p, _p, _p]),
     "nft_cg_curv": (_i, [_p, _p, _i64, _i, _d, _p, _p, _p]),
     "nft_dot_batched": (_i, [_p, _p, _i64, _i64, _i, _i, _p, _i64, _p, _p]),
     "nft_cg_curv_batched": (_i, [_p, _p, _i64, _i64, _i, _i, _d, _p, _p, _p]),
@@ -307,6 +309,45 @@ def sigmoid_pair(x, v, d):
         raise NativeError("sigmoid_pair: contiguous x, v, d of one dtype and size required")
     _check(load().nft_sigmoid_pair(ptr(x), ptr(v), ptr(d), x.numel(), dtype_code(x.dtype), stream_ptr()))
     return v, d
+
+
+LH_BERNOULLI, LH_STUDENT_T, LH_INVGAMMA = range(3)   # NFT_LH_*
+
+
+def lh_transform_pair(kind, f, t, dt):
+    """t, dt = value and derivative of likelihood `kind`'s whitening
+    transformation at f in one pass (nft_lh_transform_pair; Bernoulli:
+    -2 atan sqrt((1 - f) / f) and 1 / sqrt(f (1 - f)), fp64 arithmetic);
+    contiguous device tensors of one dtype."""
+    require_device(f, t, dt)
+    if not (f.dtype == t.dtype == dt.dtype and f.numel() == t.numel() == dt.numel()):
+        raise NativeError("lh_transform_pair: f, t, dt of one dtype and size required")
+    _check(load().nft_lh_transform_pair(int(kind), ptr(f), ptr(t), ptr(dt), f.numel(), dtype_code(f.dtype),
+                                        stream_ptr()))
+    return t, dt
+
+
+def lh_eval_batched(kind, F, p0=None, p1=None, c0=0.0, scale=1.0, value=False, grad=False, weight=False):
+    """Energy / gradient / Fisher weight of the pointwise likelihood `kind`
+    on the rows of F (k, n) in one native pass (nft_lh_eval_batched).  p0, p1:
+    fp64 device vectors of length n (or None), c0 a scalar.  Returns
+    (value (k,) fp64 | None, grad like F | None, weight like F | None) for the
+    outputs asked for."""
+    lib = load()
+    require_device(F, p0, p1)
+    if F.dim() != 2:
+        raise NativeError("lh_eval_batched: F must be (rows, n)")
+    k, n = F.shape
+    for p in (p0, p1):
+        if p is not None and (p.dtype != torch.float64 or p.numel() != n):
+            raise NativeError("lh_eval_batched: parameters are fp64 vectors of the row length")
+    val = torch.empty(k, dtype=torch.float64, device=F.device) if value else None
+    g = torch.empty_like(F) if grad else None
+    w = torch.empty_like(F) if weight else None
+    ws = workspace(k * lib.nft_reduce_workspace(n), F.device, "lh") if value else None
+    _check(lib.nft_lh_eval_batched(int(kind), ptr(F), ptr(p0), ptr(p1), float(c0), n, n, k, dtype_code(F.dtype),
+                                   float(scale), ptr(val), ptr(g), ptr(w), ptr(ws), stream_ptr()))
+    return val, g, w
 
 
 def bin_gather(src, pindex, out, pre, npix, nbins, post):

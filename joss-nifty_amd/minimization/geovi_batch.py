@@ -35,8 +35,9 @@ and the descent directions of all requesting samples come from one
 FusedCGBatch loop whose matvec applies every sample's own M_i.
 
 Supported f_lh: chains (outermost first) of ScalingOperator, DiagonalOperator,
-GeometryRemover, LOSResponse and pointwise functions (ptw_dict) ending in a
-SimpleCorrelatedField model; anything else returns None from ``plan`` and
+GeometryRemover, LOSResponse, MaskOperator / LinearInterpolator, Adder,
+BernoulliEnergy's transformation and pointwise functions (ptw_dict) ending in
+a SimpleCorrelatedField model; anything else returns None from ``plan`` and
 draw_samples keeps the per-sample path."""
 import copy
 import math
@@ -253,6 +254,41 @@ class _PtwStage:
         return G * d
 
 
+class _BernoulliStage(_PtwStage):
+    """BernoulliEnergy's transformation (energy_operators._BernoulliTransform):
+    value and derivative from one native pass (nft_lh_transform_pair); the
+    derivative is the state, as for any pointwise stage"""
+
+    def __init__(self, op):
+        self.name, self.op = "bernoulli_transform", op
+        self.args, self.kwargs = (), {}
+
+    def fwd(self, U):
+        return self.op.pair(U)
+
+
+class _AddStage:
+    """Adder on a DomainTuple: U +- a on every row; the Jacobian is the
+    identity, so there is no state"""
+
+    def __init__(self, a, neg, shape):
+        self.a = a if not torch.is_tensor(a) else a.reshape((1,) + tuple(shape))
+        self.neg = neg
+
+    def fwd(self, U):
+        return (U - self.a if self.neg else U + self.a), None
+
+    @staticmethod
+    def stack(states):
+        return None
+
+    def jvp(self, _, V):
+        return V
+
+    def vjp(self, _, G):
+        return G
+
+
 class _LinStage:
     """linear stage without state: ('scale', s) | ('diag', t) | ('reshape',) | ('los', R) |
     ('samp', R: MaskOperator / LinearInterpolator)"""
@@ -348,8 +384,11 @@ class Pipeline:
     @classmethod
     def parse(cls, f_lh):
         from ..library.correlated_fields_simple import _CorrelatedFieldModel
+        from ..domain_tuple import DomainTuple
         from ..library.los_response import LOSResponse
+        from ..operators.adder import Adder
         from ..operators.diagonal_operator import DiagonalOperator
+        from ..operators.energy_operators import _BernoulliTransform
         from ..operators.operator import _FunctionApplier, _OpChain
         from ..operators.sampling_plan import SamplingResponse
         from ..operators.scaling_operator import ScalingOperator
@@ -377,6 +416,13 @@ class Pipeline:
                 stages.append(_LinStage("samp", op, op.domain.shape, op.target.shape))
             elif isinstance(op, _FunctionApplier) and op._funcname in ptw_dict:
                 stages.append(_PtwStage(op._funcname, op._args, op._kwargs))
+            elif isinstance(op, _BernoulliTransform):
+                stages.append(_BernoulliStage(op))
+            elif isinstance(op, Adder) and isinstance(op.domain, DomainTuple) and \
+                    (np.isscalar(op._a) or not op._a.val.is_complex()):
+                # x -> x +- a (StudentTEnergy(dom, theta) @ Adder(d, neg=True) @ model)
+                a = op._a if np.isscalar(op._a) else op._a.val
+                stages.append(_AddStage(a, op._neg, op.domain.shape))
             else:
                 return None
         return cls(stages, ops[-1].layout)
@@ -733,15 +779,20 @@ def plan(minimizer, f_lh, _unused, position):
 def _likelihood(hamiltonian, positions):
     """(kind, E, icov value, scale, pipeline) of a StandardHamiltonian whose
     likelihood is GaussianEnergy(data, scaling / diagonal inverse covariance)
-    or PoissonianEnergy (optionally scaled) on a supported model chain, else
-    None."""
+    or PoissonianEnergy, or a pointwise likelihood of nft_lh_eval_batched
+    (BernoulliEnergy, StudentTEnergy, InverseGammaEnergy; kind "pointwise")
+    (optionally scaled) on a supported model chain, else None."""
     from ..operators.diagonal_operator import DiagonalOperator
-    from ..operators.energy_operators import GaussianEnergy, PoissonianEnergy, _LikelihoodChain
+    from ..operators.energy_operators import (BernoulliEnergy, GaussianEnergy, InverseGammaEnergy,
+                                              PoissonianEnergy, StudentTEnergy, _LikelihoodChain)
     from ..operators.scaling_operator import ScalingOperator
     lh = hamiltonian.likelihood_energy
     if not isinstance(lh, _LikelihoodChain):
         return None
-    ops = list(lh._op._ops)
+    def flat(chain):
+        # nested likelihood chains (lh.scale(f), (E @ Adder) @ model) opened up
+        return [o for op in chain._op._ops for o in (flat(op) if isinstance(op, _LikelihoodChain) else [op])]
+    ops = flat(lh)
     scale = 1.0
     if isinstance(ops[0], ScalingOperator):      # scaled likelihood (lh.scale(f))
         scale = float(np.real(ops[0]._factor))
@@ -761,6 +812,8 @@ def _likelihood(hamiltonian, positions):
         kind = "gauss"
     elif isinstance(E, PoissonianEnergy):
         kind = "poisson"
+    elif isinstance(E, (BernoulliEnergy, StudentTEnergy, InverseGammaEnergy)):
+        kind = "pointwise"
     else:
         return None
     pipe = Pipeline.parse(ops[1:])
@@ -774,7 +827,8 @@ def kl_batch(hamiltonian, positions):
     batched pass (SampledKLEnergyClass, kl_energies.py:295-356: its per
     sample H(Linearization.make_var(s)) evaluations), or None if the
     likelihood is not a GaussianEnergy(data, scaling / diagonal inverse
-    covariance) or PoissonianEnergy applied to a supported model chain.
+    covariance), PoissonianEnergy, BernoulliEnergy, StudentTEnergy or
+    InverseGammaEnergy applied to a supported model chain.
 
     Returns ([value_i], [gradient_i MultiField])."""
     # one position too: per row the batched pass does not depend on the
@@ -797,6 +851,13 @@ def kl_batch(hamiltonian, positions):
         h = _rowdots([(R, W), (X, X)])
         lval = 0.5 * h[0]
         gs = W
+    elif kind == "pointwise":
+        # value and gradient (times the likelihood's scale) from one native pass
+        code, p0, p1, c0 = E._lh_kernel_args()
+        lv, gs, _ = _native.lh_eval_batched(code, S.contiguous(), p0, p1, c0, scale, value=True, grad=True)
+        h = np.stack([lv.cpu().numpy(), _rowdots([(X, X)])[0]])
+        lval = h[0]
+        scale = 1.0
     else:
         d = E._dfloat.val.reshape(1, -1)
         D = d.expand_as(S).contiguous()
@@ -826,7 +887,8 @@ def kl_metric_batch(hamiltonian, positions):
     H(Linearization.make_var(s, want_metric=True)) rebuild) linearised ONCE
     at the k local sample positions and applied to all of them in one batched
     pass: M_s x = J_s^T W_s J_s x + x with W_s the likelihood's Fisher metric
-    at s (Gaussian: the inverse covariance; Poissonian: 1 / lambda_s; times
+    at s (Gaussian: the inverse covariance; Poissonian: 1 / lambda_s;
+    Bernoulli / Student-t / inverse gamma: nft_lh_eval_batched's weight; times
     the likelihood scale) and the identity of the standard prior.
 
     Returns a callable x -> [M_s x for every local sample] (MultiFields, in
@@ -845,6 +907,12 @@ def kl_metric_batch(hamiltonian, positions):
     Sf, states = pipe.fwd(X)
     if kind == "gauss":
         W = icv if isinstance(icv, float) else icv.reshape((1,) + tuple(Sf.shape[1:]))
+    elif kind == "pointwise":
+        # the Fisher weight (times the likelihood's scale) from one native pass
+        code, p0, p1, c0 = E._lh_kernel_args()
+        W = _native.lh_eval_batched(code, Sf.reshape(k, -1).contiguous(), p0, p1, c0, scale,
+                                    weight=True)[2].reshape(Sf.shape)
+        scale = 1.0
     else:
         W = 1. / Sf
     if scale != 1.0:

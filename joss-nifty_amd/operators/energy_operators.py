@@ -1,5 +1,6 @@
 """Energy operators on the sampling path (src/operators/energy_operators.py):
-GaussianEnergy (:478-583), PoissonianEnergy (:586-625), StandardHamiltonian
+GaussianEnergy (:478-583), PoissonianEnergy (:586-625), InverseGammaEnergy,
+StudentTEnergy and BernoulliEnergy (:628-761), StandardHamiltonian
 (:764-831), the likelihood chain (:152-200) and the quadratic forms."""
 from functools import reduce
 from operator import add
@@ -334,6 +335,149 @@ class PoissonianEnergy(LikelihoodEnergyOperator):
 
     def get_transformation(self):
         return np.float64, 2. * Operator.identity_operator(self._domain).sqrt()
+
+
+def _flat64(field, cache, key):
+    """the values of a real Field as a flat fp64 vector (parameter array of
+    nft_lh_eval_batched), made once"""
+    if key not in cache:
+        cache[key] = field.val.reshape(-1).to(__import__("torch").float64).contiguous()
+    return cache[key]
+
+
+class InverseGammaEnergy(LikelihoodEnergyOperator):
+    """sum (alpha + 1) log(f) + beta / f (energy_operators.py:628-680)."""
+
+    def __init__(self, beta, alpha=-0.5):
+        from ..sugar import makeOp
+        from .simplify_for_const import ConstantOperator
+        if not isinstance(beta, Field):
+            raise TypeError("beta must be a Field")
+        self._domain = DomainTuple.make(beta.domain)
+        self._beta = beta
+        if np.isscalar(alpha):
+            alpha = Field(beta.domain, np.full(beta.shape, alpha))
+        elif not isinstance(alpha, Field):
+            raise TypeError("alpha must be a scalar or a Field")
+        self._alphap1 = alpha + 1
+        if utilities.numpy_dtype(beta.dtype) != np.float64:
+            raise TypeError("beta must be float64")
+        self._sampling_dtype = _field_dtype(beta)
+        self._kargs = {}
+        super().__init__(2 * ConstantOperator(self._beta, domain=self._domain),
+                         lambda x: makeOp(x.reciprocal().sqrt()))
+
+    def apply(self, x):
+        self._check_input(x)
+        res = x.log().vdot(self._alphap1) + x.reciprocal().vdot(self._beta)
+        if not x.want_metric:
+            return res
+        return res.add_metric(self.get_metric_at(x.val))
+
+    def get_transformation(self):
+        from ..sugar import makeOp
+        return self._sampling_dtype, makeOp(self._alphap1.sqrt()) @ Operator.identity_operator(self._domain).log()
+
+    def _lh_kernel_args(self):
+        """(kind, p0, p1, c0) of nft_lh_eval_batched"""
+        from .. import _native
+        return (_native.LH_INVGAMMA, _flat64(self._alphap1, self._kargs, "a"),
+                _flat64(self._beta, self._kargs, "b"), 0.0)
+
+
+class StudentTEnergy(LikelihoodEnergyOperator):
+    """sum (theta + 1) / 2 log1p(f^2 / theta) (energy_operators.py:683-720);
+    theta a scalar or a Field."""
+
+    def __init__(self, domain, theta):
+        self._domain = DomainTuple.make(domain)
+        self._theta = theta
+        self._kargs = {}
+        super().__init__(Operator.identity_operator(self._domain), lambda x: self.get_metric_at(x).get_sqrt())
+
+    def apply(self, x):
+        self._check_input(x)
+        res = (((self._theta + 1) / 2) * (x ** 2 / self._theta).log1p()).sum()
+        if not x.want_metric:
+            return res
+        return res.add_metric(self.get_metric_at(x.val))
+
+    def get_transformation(self):
+        from ..sugar import full, makeOp
+        th = self._theta
+        if not isinstance(th, (Field, MultiField)):
+            th = full(self._domain, th)
+        return np.float64, makeOp(((th + 1) / (th + 3)).sqrt())
+
+    def _lh_kernel_args(self):
+        from .. import _native
+        if isinstance(self._theta, Field):
+            return _native.LH_STUDENT_T, _flat64(self._theta, self._kargs, "t"), None, 0.0
+        return _native.LH_STUDENT_T, None, None, float(self._theta)
+
+
+class _BernoulliTransform(Operator):
+    """t(f) = -2 arctan(sqrt((1 - f) / f)): the map whose Jacobian squares to
+    Bernoulli's Fisher metric 1 / (f (1 - f)).  The reference builds it from an
+    operator product (energy_operators.py:757-761); here it is ONE pointwise
+    operator whose value and derivative come from one native pass
+    (nft_lh_transform_pair), so it stays a chain link that the sandwich
+    fusion and the batched geoVI pipeline understand."""
+
+    def __init__(self, domain):
+        self._domain = self._target = DomainTuple.make(domain)
+
+    @staticmethod
+    def pair(f):
+        """(t, dt/df) tensors at the tensor f"""
+        import torch
+        from .. import _native
+        if f.dtype not in (torch.float64, torch.float32):
+            f = f.to(torch.float64)
+        f = f.contiguous()
+        return _native.lh_transform_pair(_native.LH_BERNOULLI, f, torch.empty_like(f), torch.empty_like(f))
+
+    def apply(self, x):
+        from ..sugar import makeOp
+        self._check_input(x)
+        lin = x.jac is not None
+        t, dt = self.pair((x.val if lin else x).val)
+        if not lin:
+            return Field(self._domain, t)
+        return x.new(Field(self._domain, t), makeOp(Field(self._domain, dt))(x.jac))
+
+    def __repr__(self):
+        return "_BernoulliTransform"
+
+
+class BernoulliEnergy(LikelihoodEnergyOperator):
+    """-d^T log(f) - (1 - d)^T log(1 - f) for events d in {0, 1}
+    (energy_operators.py:723-761)."""
+
+    def __init__(self, d):
+        if not isinstance(d, Field) or not np.issubdtype(utilities.numpy_dtype(d.dtype), np.integer):
+            raise TypeError("data must be a Field of integers")
+        if bool(((d.val != 0) & (d.val != 1)).any().item()):
+            raise ValueError("data must hold only 0 (no event) and 1 (event)")
+        self._d = d
+        self._dfloat = Field(d.domain, d.val.to(__import__("torch").float64))
+        self._domain = DomainTuple.make(d.domain)
+        self._kargs = {}
+        super().__init__(Adder(self._dfloat, neg=True), lambda x: self.get_metric_at(x).get_sqrt())
+
+    def apply(self, x):
+        self._check_input(x)
+        res = -x.log().vdot(self._dfloat) + (1. - x).log().vdot(self._dfloat - 1.)
+        if not x.want_metric:
+            return res
+        return res.add_metric(self.get_metric_at(x.val))
+
+    def get_transformation(self):
+        return np.float64, _BernoulliTransform(self._domain)
+
+    def _lh_kernel_args(self):
+        from .. import _native
+        return _native.LH_BERNOULLI, _flat64(self._dfloat, self._kargs, "d"), None, 0.0
 
 
 class StandardHamiltonian(EnergyOperator):

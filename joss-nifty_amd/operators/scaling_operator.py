@@ -55,7 +55,16 @@ class ScalingOperator(EndomorphicOperator):
         return ScalingOperator(self._domain, fct, self._dtype)
 
     def __call__(self, x):
-        return super().__call__(x)
+        # a non-negative factor carries a metric along (scaling_operator.py:
+        # 126-135): f * E has the metric sqrt(f) M sqrt(f) (lh.scale(f) under
+        # want_metric)
+        res = super().__call__(x)
+        if np.isreal(self._factor) and self._factor >= 0 and getattr(x, "jac", None) is not None \
+                and x.metric is not None:
+            from .sandwich_operator import SandwichOperator
+            newop = ScalingOperator(x.metric.domain, np.sqrt(self._factor), self._dtype)
+            res = res.add_metric(SandwichOperator.make(newop, x.metric))
+        return res
 
     def __repr__(self):
         return f"ScalingOperator ({self._factor})"

@@ -9,6 +9,28 @@ from ..multi_field import MultiField
 from .operator import Operator
 
 
+class ConstantOperator(Operator):
+    """Maps everything on `domain` to the fixed field `output`
+    (simplify_for_const.py:64-80); its Jacobian is a NullOperator."""
+
+    def __init__(self, output, domain={}):
+        from ..sugar import makeDomain
+        self._domain = makeDomain(domain)
+        self._target = makeDomain(output.domain)
+        self._output = output
+
+    def apply(self, x):
+        from .simple_linear_operators import NullOperator
+        self._check_input(x)
+        if x.jac is None:
+            return self._output
+        return x.new(self._output, NullOperator(self._domain, self._target))
+
+    def __repr__(self):
+        tgt = self.target.keys() if isinstance(self.target, MultiDomain) else "()"
+        return f"{tgt} <- ConstantOperator"
+
+
 class InsertionOperator(Operator):
     def __init__(self, target, cst_field):
         from .simple_linear_operators import PartialExtractor
