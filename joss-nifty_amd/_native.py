@@ -84,6 +84,7 @@ SIGNATURES = {
     "nft_amp_vjp_batched": (_i, [_p, _p, _p, _p, _p, _i, _i64, _i64, _p]),
     "nft_hartley_cg_blocks": (_i, [_i, _p, _i, _p, _i]),
     "nft_hartley_dir_blocks": (_i, [_i, _p]),
+    "nft_hartley_pro_rows": (_i, [_i, _p]),
     "nft_cg_update_seg_batched": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i, _i, _d, _p, _p, _i, _i, _p]),
     "nft_cg_update_seg2_batched": (_i, [_p, _p, _p, _p, _i64, _i, _i64, _i64, _i, _i64, _i, _i, _d, _p, _p, _i, _p]),
     "nft_cg_direction_dd2_batched": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i, _i, _p, _d, _p, _i64, _i64, _p]),
@@ -472,6 +473,13 @@ def hartley_dir_blocks(grid):
     """blocks (d.d partials per item) of the folded prologue over `grid`"""
     sh = (ctypes.c_int64 * len(grid))(*[int(n) for n in grid])
     return int(load().nft_hartley_dir_blocks(len(grid), sh))
+
+
+def hartley_pro_rows(grid):
+    """1 where the row-staged prologue serves `grid` (hartley_dir_blocks then
+    counts its groups of mirror rows), else 0"""
+    sh = (ctypes.c_int64 * len(grid))(*[int(n) for n in grid])
+    return int(load().nft_hartley_pro_rows(len(grid), sh))
 
 
 def _set_lazy(f, lz):

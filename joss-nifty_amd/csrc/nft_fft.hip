@@ -1570,6 +1570,13 @@ int nft_hartley_dir_blocks(int ndim, const int64_t* shape) {
   return (int)((ncell + 255) / 256);
 }
 
+int nft_hartley_pro_rows(int ndim, const int64_t* shape) {
+  if (ndim < 1 || ndim > 3 || !shape) return 0;
+  for (int a = 0; a < ndim; ++a)
+    if (shape[a] < 1) return 0;
+  return pro_rows_ok(ndim, shape[ndim - 1]) ? 1 : 0;
+}
+
 int nft_hartley_cg_blocks(int ndim, const int64_t* shape, int naxes, const int* axes, int dtype) {
   using namespace fast;
   Geo g;

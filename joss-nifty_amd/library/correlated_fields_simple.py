@@ -704,9 +704,7 @@ class CFJacobian(LinearOperator):
 
     # The three phases of metric_flat_batch.  Only mv_grid touches the grid
     # segment of D and Q; the amplitude phases read / write the amplitude keys
-    # alone, so a caller may run them on a second stream next to the grid
-    # segment's CG work (fused_cg.FusedCGBatch).  Their buffers persist per
-    # batch size: no allocation is freed while another stream may use it.
+    # alone.  Their buffers persist per batch size.
     def _mv_bufs(self, k, dtype=torch.float64):
         """the phases' buffers for k rows of storage dtype (fp64, or fp32 for
         the fp32-storage CG: every grid operand and dA in fp32)"""
@@ -822,7 +820,7 @@ class CFJacobian(LinearOperator):
         """the carried iteration can defer its iterate (nft_hartley_fuse.lazy_*):
         the direction is carried by the row-staged prologue"""
         grid = tuple(self._afull.shape)
-        return self.dir_blocks(k) > 0 and 2 <= len(grid) <= 3 and grid[-1] // 2 + 1 <= 2556
+        return self.dir_blocks(k) > 0 and _native.hartley_pro_rows(grid) == 1
 
     def grid_size(self):
         """elements of the grid key (the grid segment without its padding)"""

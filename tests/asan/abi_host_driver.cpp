@@ -59,6 +59,13 @@ int main() {
     CHECK(nft_hartley_fused(nullptr, nullptr, nullptr, 2, shape, 2, bad_axes, 0, 0, 1.0, nullptr, 0, nullptr) ==
           NFT_ERR_ARG);
   }
+  // folded prologue: the row-staged bound (n_last / 2 + 1 <= 2556) and its block counts
+  {
+    int64_t in[2] = {4, 5110}, out[2] = {4, 5112}, one[1] = {2048};
+    CHECK(nft_hartley_pro_rows(2, in) == 1 && nft_hartley_dir_blocks(2, in) == 3);
+    CHECK(nft_hartley_pro_rows(2, out) == 0 && nft_hartley_dir_blocks(2, out) == 30);
+    CHECK(nft_hartley_pro_rows(1, one) == 0 && nft_hartley_pro_rows(2, nullptr) == 0);
+  }
   // reduction / CG / amplitude / bin sizing
   for (int64_t n : {1LL, 255LL, 256LL, 4194304LL, 4821009LL}) {
     CHECK(nft_reduce_workspace(n) > 0);

@@ -32,10 +32,15 @@ def test_library_exports_every_header_symbol():
 
 def test_folded_prologue_block_count():
     """nft_hartley_dir_blocks (pure host arithmetic): 2-D / 3-D grids with
-    n_last/2+1 <= 2560 take the row-staged prologue, one block per group of
-    mirror rows (prod over the leading axes of n/2+1); 1-D and longer rows
-    the cell grid prod(n/2+1), last axis padded to 64, 256 cells per block"""
+    n_last/2+1 <= 2556 (PRO_ROWS_MAXH of nft_fft.hip) take the row-staged
+    prologue, one block per group of mirror rows (prod over the leading axes
+    of n/2+1); 1-D and longer rows the cell grid prod(n/2+1), last axis padded
+    to 64, 256 cells per block"""
     from nifty_amd import _native
+    # n_last/2+1 = 2556: the last row-staged length; 2557 cells pad to 2560
+    assert _native.hartley_dir_blocks((4, 5110)) == 3 and _native.hartley_pro_rows((4, 5110)) == 1
+    assert _native.hartley_dir_blocks((4, 5112)) == 30 and _native.hartley_pro_rows((4, 5112)) == 0
+    assert _native.hartley_pro_rows((2048,)) == 0
     assert _native.hartley_dir_blocks((2048, 2048)) == 1025
     assert _native.hartley_dir_blocks((64, 30)) == 33
     assert _native.hartley_dir_blocks((8, 8, 130)) == 5 * 5
