@@ -34,6 +34,9 @@
  *                      model: _TwoLogIntegrations, _SlopeRemover, _Normalization,
  *                      fluctuation/zero-mode scaling (src/library/correlated_fields.py:
  *                      91-201, correlated_fields_simple.py:86-127), linearised
+ *   nft_matern_*       value and Jacobian of the Matern amplitude _AmplitudeMatern
+ *                      (src/library/correlated_fields.py:233-274) of
+ *                      CorrelatedFieldMaker.add_fluctuations_matern, closed form
  *   nft_los_*          LOSResponse.apply on a box-blocked layout of the same COO
  *                      matrix, src/library/los_response.py:180-233
  *   nft_spmv_*         LOSResponse.apply (scipy COO matvec / rmatvec),
@@ -779,6 +782,70 @@ int nft_amp_forward_batched(const nft_amp_model* model, const double* x_fl, cons
                             const double* x_spec, int64_t lat_stride, int nrow, double* a,
                             int64_t a_stride, double* buf, int64_t buf_stride,
                             nft_amp_const* item_consts, double* ws, hipStream_t stream);
+
+/* ---- Matern-kernel amplitude (csrc/nft_matern.hip) --------------------- */
+/* The parametric amplitude of CorrelatedFieldMaker.add_fluctuations_matern
+ * (src/library/correlated_fields.py:233-274 with the zero-mode and volume
+ * factors of :360-384), fp64, B power bins:
+ *   A_0 = V zm (0 without a zero mode),  A_b = sqrt(V) s (1 + u_b)^(l/4),
+ *   u_b = k2[b] / c^2,  s = exp(lm_s + ls_s x_scale),  c = exp(lm_c + ls_c
+ *   x_cutoff),  l = mu_l + sig_l x_slope,  zm = exp(lm_o + ls_o x_zm),
+ *   V = total_volume.
+ * Key order in every pointer array: scale, cutoff, loglogslope, zeromode
+ * (entry 3 is ignored without a zero mode).  The kernels use no atomics and
+ * no device-global state: calls on different streams are independent. */
+typedef struct nft_matern_model {
+  const double* k2; /* [B] squared k-lengths, device */
+  double lm_s, ls_s, lm_c, ls_c, mu_l, sig_l, lm_o, ls_o, total_volume;
+  int64_t B;
+  int has_zm;
+} nft_matern_model;
+/* One linearisation: the three FINISHED Jacobian columns, B values each with
+ * entry 0 = 0 (device pointers),
+ *   gs = ls_s A,  gc = -(l ls_c / 2) A u / (1 + u),  gl = (sig_l / 4) A log1p(u),
+ * and the scalars of the point; the zero-mode column is the single entry
+ * total_volume * zm * ls_o at bin 0. */
+typedef struct nft_matern_const {
+  const double *gs, *gc, *gl;
+  double l, zm, ls_s, sig_l, ls_c, ls_o, total_volume;
+  int64_t B;
+  int has_zm;
+} nft_matern_const;
+/* doubles per row of buf (three columns, each padded to an even length) */
+int64_t nft_matern_forward_buf(int64_t B);
+/* bytes of VJP workspace per right-hand side */
+size_t nft_matern_workspace(int64_t B);
+/* Amplitude and linearisation at nrow latent points in one launch (x pointers
+ * advance by lat_stride per row): a[r * a_stride + b], the columns in
+ * buf[r * buf_stride ..] (buf_stride >= nft_matern_forward_buf(B); an even
+ * stride keeps the columns 16-byte aligned) and item_consts[r], a DEVICE
+ * nft_matern_const pointing into buf, written by the kernel.  No value goes
+ * through the host. */
+int nft_matern_forward_batched(const nft_matern_model* model, const double* x_scale, const double* x_cutoff,
+                               const double* x_slope, const double* x_zm, int64_t lat_stride, int nrow, double* a,
+                               int64_t a_stride, double* buf, int64_t buf_stride, nft_matern_const* item_consts,
+                               hipStream_t stream);
+/* da[r * da_stride + b * da_elem_stride] = sum_j G_j[b] t[j][r * lat_stride]
+ * for nrhs tangents (da_elem_stride 0: 1; da_stride 1 with da_elem_stride
+ * nrhs is the bin-major layout of nft_hartley_fuse.c_estride).  item_mode as
+ * nft_amp2_jvp: 0 = every RHS uses *c, 1 = item_consts is a DEVICE array of
+ * nrhs sets, 2 = item_consts is ONE device set shared by all; *c gives B and
+ * has_zm in every mode.  dtype must be 0 (fp64).  Right-hand side r of a
+ * batched call is bitwise the nrhs = 1 call.  NFT_ERR_ARG for B < 2,
+ * nrhs < 1, a NULL required pointer, or strides that make rows overlap. */
+int nft_matern_jvp_batched(const nft_matern_const* c, const nft_matern_const* item_consts, int item_mode,
+                           const double* const* t, int64_t lat_stride, double* da, int64_t da_stride,
+                           int64_t da_elem_stride, int nrhs, int dtype, hipStream_t stream);
+/* out[j][r * lat_stride] = shift * d[j][r * lat_stride] + sum_b G_j[b]
+ * g[r * g_stride + b] (d NULL or shift 0: no d term).  Two launches:
+ * per-workgroup partials (wave shuffle trees and LDS) into ws, then one
+ * fixed-order fold per RHS whose order depends on B alone, so RHS r of a
+ * batched call is bitwise the nrhs = 1 call.  ws: nrhs *
+ * nft_matern_workspace(B) bytes.  NFT_ERR_ARG as above; for nrhs > 1
+ * g_stride >= B and lat_stride >= 1. */
+int nft_matern_vjp_batched(const nft_matern_const* c, const nft_matern_const* item_consts, int item_mode,
+                           const double* g, int64_t g_stride, double* const* out, const double* const* d,
+                           int64_t lat_stride, double shift, double* ws, int nrhs, hipStream_t stream);
 
 /* ---- launch profiler (HIP events) -------------------------------------- */
 /* Between nft_prof_begin and nft_prof_end every hot-path kernel launch

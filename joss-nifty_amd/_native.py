@@ -103,6 +103,12 @@ SIGNATURES = {
                           _p, _p]),
     "nft_amp_forward_buf": (_i64, [_i64]),
     "nft_amp_forward_batched": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i, _p, _i64, _p, _i64, _p, _p, _p]),
+    # Matern amplitude: no device-global state, any stream
+    "nft_matern_forward_buf": (_i64, [_i64]),
+    "nft_matern_workspace": (_sz, [_i64]),
+    "nft_matern_forward_batched": (_i, [_p, _p, _p, _p, _p, _i64, _i, _p, _i64, _p, _i64, _p, _p]),
+    "nft_matern_jvp_batched": (_i, [_p, _p, _i, _p, _i64, _p, _i64, _i64, _i, _i, _p]),
+    "nft_matern_vjp_batched": (_i, [_p, _p, _i, _p, _i64, _p, _p, _i64, _d, _p, _i, _p]),
 }
 
 
@@ -152,6 +158,20 @@ class AmpModel(ctypes.Structure):
                [(n, _d) for n in ("lm_f", "ls_f", "mu_s", "sig_s", "lm_x", "ls_x", "lm_a", "ls_a", "lm_o", "ls_o",
                                   "total_volume")] + \
                [("B", _i64), ("has_flex", _i), ("has_asp", _i), ("has_zm", _i)]
+
+
+class MaternModel(ctypes.Structure):
+    """nft_matern_model (include/nifty_amd.h)."""
+    _fields_ = [("k2", _p)] + \
+               [(n, _d) for n in ("lm_s", "ls_s", "lm_c", "ls_c", "mu_l", "sig_l", "lm_o", "ls_o", "total_volume")] + \
+               [("B", _i64), ("has_zm", _i)]
+
+
+class MaternConst(ctypes.Structure):
+    """nft_matern_const (include/nifty_amd.h)."""
+    _fields_ = [(n, _p) for n in ("gs", "gc", "gl")] + \
+               [(n, _d) for n in ("l", "zm", "ls_s", "sig_l", "ls_c", "ls_o", "total_volume")] + \
+               [("B", _i64), ("has_zm", _i)]
 
 
 class AmpOut(ctypes.Structure):

@@ -226,9 +226,16 @@ class CorrelatedFieldMaker:
     fused SimpleCorrelatedField operator (native prologue/epilogue Hartley
     engine, carried-CG Jacobian): the reference's operator tree for that case
     is algebraically the same map (test_complicated_vs_simple,
-    test/test_operators/test_correlated_fields.py:214-272).  Every other case
-    (product spectra, Matern components, a unit or operator-valued zero mode,
-    a field offset) is built as the reference's operator tree
+    test/test_operators/test_correlated_fields.py:214-272).  ONE
+    `add_fluctuations_matern` component under the same conditions (single
+    RGSpace with an RGSpace harmonic partner, zero mode disabled or
+    LogNormal, `offset_mean` a scalar or None) returns the fused Matern field
+    (`_MaternFieldModel`: the same engine with the closed-form amplitude of
+    library/matern.py and the nft_matern_* kernels), and `amplitude` its fused
+    amplitude operator.  Every other case
+    (product spectra, a Matern component beside another one, a unit or
+    operator-valued zero mode, a field offset) is built as the reference's
+    operator tree
     (:764-823) on the device operators: per-component fused amplitudes,
     PowerDistributor + ContractionOperator broadcasts, and the native
     Hartley transform per sub-space.  `total_N > 0` (stacked field models,
@@ -290,11 +297,15 @@ class CorrelatedFieldMaker:
             harmonic_partner.check_codomain(target_subdomain)
         target_subdomain = makeDomain(target_subdomain)
         pre = self._prefix + prefix
+        params = (tuple(scale), tuple(cutoff), tuple(loglogslope))
         scale = LognormalTransform(*scale, pre + 'scale', 0)
         cutoff = LognormalTransform(*cutoff, pre + 'cutoff', 0)
         loglogslope = NormalTransform(*loglogslope, pre + 'loglogslope', 0)
         totvol = target_subdomain[-1].total_volume if adjust_for_volume else 1.
         amp = _AmplitudeMatern(PowerSpace(harmonic_partner), scale, cutoff, loglogslope, totvol)
+        # what the fused field (finalize) builds its closed-form amplitude from
+        amp.matern_params = params + (pre, float(totvol))
+        amp.harmonic_partner = harmonic_partner
         self._a.append(amp)
         self._target_subdomains.append(target_subdomain)
 
@@ -324,9 +335,9 @@ class CorrelatedFieldMaker:
 
     # ------------------------------------------------------------ lowering
     def _fusable(self):
-        """One non-parametric component on an RGSpace, zero mode off or
-        LogNormal: the case the fused operator restates exactly."""
-        if len(self._a) != 1 or not hasattr(self._a[0], "model"):
+        """One non-parametric or one Matern component on an RGSpace, zero
+        mode off or LogNormal: the cases the fused operators restate exactly."""
+        if len(self._a) != 1 or not (hasattr(self._a[0], "model") or hasattr(self._a[0], "matern_params")):
             return False
         if not (self._azm is not None and (self._offset_std is not None
                                            or (np.isscalar(self._azm) and self._azm == 0))):
@@ -335,8 +346,13 @@ class CorrelatedFieldMaker:
         return len(tgt) == 1 and _rg_only(tgt) and _rg_only((self._a[0].harmonic_partner,))
 
     def _fused_model(self, offset_mean):
-        from .correlated_fields_simple import _CorrelatedFieldModel
+        from .correlated_fields_simple import _CorrelatedFieldModel, _MaternFieldModel
         a = self._a[0]
+        if hasattr(a, "matern_params"):
+            scale, cutoff, slope, pre, totvol = a.matern_params
+            return _MaternFieldModel(self._target_subdomains[0][0], a.harmonic_partner, offset_mean,
+                                     self._offset_std, scale, cutoff, slope, totvol, pre,
+                                     xi_prefix=self._prefix)
         fl, flex, asp, slope, pre = a.params
         return _CorrelatedFieldModel(self._target_subdomains[0][0], a.harmonic_partner, offset_mean,
                                      self._offset_std, fl, flex, asp, slope, pre, xi_prefix=self._prefix)

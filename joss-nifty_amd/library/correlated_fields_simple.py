@@ -914,7 +914,11 @@ class CFJacobian(LinearOperator):
         stop = lay.offsets[i + 1] if i + 1 < len(lay.keys) else lay.size
         return o, stop
 
-    supports_fp32 = True
+    @property
+    def supports_fp32(self):
+        """fp32 CG storage (config.set_cg_precision): where the amplitude's
+        kernels take it; a solve with another amplitude stays fp64"""
+        return getattr(self._m.amp, "supports_fp32", True)
 
     def _metric_flat_batch32(self, D, Q, W, shift):
         """metric_flat_batch on fp32 storage (config.set_cg_precision("fp32")):
@@ -987,17 +991,14 @@ class CFJacobian(LinearOperator):
         self._adjoint_t(g, lay.views(q), dv, shift)
 
 
-class _CorrelatedFieldModel(Operator):
-    """The fused correlated field.  `prefix` names the amplitude keys;
-    `xi_prefix` (default: `prefix`) names 'xi' and 'zeromode', which the
-    CorrelatedFieldMaker keys by the maker's prefix alone
-    (correlated_fields.py:578-581,759,806)."""
+class _FusedFieldBase(Operator):
+    """The fused correlated field  s = offset_mean + c_h HT[A[pindex] * xi]
+    for an amplitude model `amp` (the duck-typed interface of _AmplitudeModel
+    / matern._MaternAmplitudeModel): everything but the construction of the
+    amplitude.  `xp` prefixes the 'xi' key."""
 
-    def __init__(self, target, harmonic_partner, offset_mean, offset_std, fluctuations, flexibility,
-                 asperity, loglogavgslope, prefix, xi_prefix=None):
-        xp = prefix if xi_prefix is None else xi_prefix
-        self.amp = _AmplitudeModel(target, harmonic_partner, offset_std, fluctuations, flexibility,
-                                   asperity, loglogavgslope, prefix, zm_prefix=xp)
+    def __init__(self, amp, target, harmonic_partner, offset_mean, xp):
+        self.amp = amp
         self.k_xi = xp + "xi"
         dom = dict(self.amp.domain_dict)
         dom[self.k_xi] = DomainTuple.make(harmonic_partner)
@@ -1084,8 +1085,39 @@ class _CorrelatedFieldModel(Operator):
             return None
         return res, jac
 
+
+class _CorrelatedFieldModel(_FusedFieldBase):
+    """The fused correlated field with the non-parametric amplitude.
+    `prefix` names the amplitude keys; `xi_prefix` (default: `prefix`) names
+    'xi' and 'zeromode', which the CorrelatedFieldMaker keys by the maker's
+    prefix alone (correlated_fields.py:578-581,759,806)."""
+
+    def __init__(self, target, harmonic_partner, offset_mean, offset_std, fluctuations, flexibility,
+                 asperity, loglogavgslope, prefix, xi_prefix=None):
+        xp = prefix if xi_prefix is None else xi_prefix
+        amp = _AmplitudeModel(target, harmonic_partner, offset_std, fluctuations, flexibility,
+                              asperity, loglogavgslope, prefix, zm_prefix=xp)
+        super().__init__(amp, target, harmonic_partner, offset_mean, xp)
+
     def __repr__(self):
         return f"SimpleCorrelatedField (fused) {self._target.shape}"
+
+
+class _MaternFieldModel(_FusedFieldBase):
+    """The fused correlated field of ONE add_fluctuations_matern component
+    (library/matern.py): the same transforms, bin gather, Jacobian and carried
+    CG as _CorrelatedFieldModel, with the closed-form Matern amplitude."""
+
+    def __init__(self, target, harmonic_partner, offset_mean, offset_std, scale, cutoff, loglogslope,
+                 total_volume, prefix, xi_prefix=None):
+        from .matern import _MaternAmplitudeModel
+        xp = prefix if xi_prefix is None else xi_prefix
+        amp = _MaternAmplitudeModel(harmonic_partner, offset_std, scale, cutoff, loglogslope, total_volume,
+                                    prefix, zm_prefix=xp)
+        super().__init__(amp, target, harmonic_partner, offset_mean, xp)
+
+    def __repr__(self):
+        return f"Matern correlated field (fused) {self._target.shape}"
 
 
 def SimpleCorrelatedField(target, offset_mean, offset_std, fluctuations, flexibility, asperity,

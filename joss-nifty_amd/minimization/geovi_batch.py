@@ -383,7 +383,7 @@ class Pipeline:
 
     @classmethod
     def parse(cls, f_lh):
-        from ..library.correlated_fields_simple import _CorrelatedFieldModel
+        from ..library.correlated_fields_simple import _FusedFieldBase
         from ..domain_tuple import DomainTuple
         from ..library.los_response import LOSResponse
         from ..operators.adder import Adder
@@ -398,7 +398,7 @@ class Pipeline:
             ops = [o for op in f_lh for o in (op._ops if isinstance(op, _OpChain) else (op,))]
         else:
             ops = list(f_lh._ops) if isinstance(f_lh, _OpChain) else [f_lh]
-        if not ops or not isinstance(ops[-1], _CorrelatedFieldModel):
+        if not ops or not isinstance(ops[-1], _FusedFieldBase):
             return None
         stages = [_CFStage(ops[-1])]
         for op in reversed(ops[:-1]):
