@@ -37,6 +37,10 @@
  *   nft_matern_*       value and Jacobian of the Matern amplitude _AmplitudeMatern
  *                      (src/library/correlated_fields.py:233-274) of
  *                      CorrelatedFieldMaker.add_fluctuations_matern, closed form
+ *   nft_prod_*,        CorrelatedFieldMaker.finalize with two add_fluctuations
+ *   nft_mirror_mix     components (src/library/correlated_fields.py:764-823): the
+ *                      amplitude table over the combined bins and the frame change
+ *                      between the separable and the joint Hartley transform
  *   nft_los_*          LOSResponse.apply on a box-blocked layout of the same COO
  *                      matrix, src/library/los_response.py:180-233
  *   nft_spmv_*         LOSResponse.apply (scipy COO matvec / rmatvec),
@@ -846,6 +850,63 @@ int nft_matern_jvp_batched(const nft_matern_const* c, const nft_matern_const* it
 int nft_matern_vjp_batched(const nft_matern_const* c, const nft_matern_const* item_consts, int item_mode,
                            const double* g, int64_t g_stride, double* const* out, const double* const* d,
                            int64_t lat_stride, double shift, double* ws, int nrhs, hipStream_t stream);
+
+/* ---- product-spectrum correlated fields (csrc/nft_prod.hip) ------------- */
+/* Two add_fluctuations components on a product domain (space x energy, space
+ * x time) run on the one-space engine in the frame xi' = R xi,
+ *   R = (P1 + P2 + I - P1 P2) / 2,   H_1 (x) H_2 = R H_joint = H_joint R,
+ * P_g the point mirror k -> -k on the grid axes of group g (R is symmetric,
+ * orthogonal and an involution).  No atomics, no device-global state. */
+/* y[r * y_stride + k] = (R x[r * x_stride + .])[k] for nrow rows of an
+ * ndim-axis grid (2 <= ndim <= 3), axes [0, split) in group 1 and
+ * [split, ndim) in group 2, summed as ((x + P1 x) + P2 x - P1 P2 x) * 0.5.
+ * Works in place (y == x with equal strides): a thread owns whole orbits
+ * {k, P1 k, P2 k, P1 P2 k}; x and y must not overlap otherwise.  dtype 0 =
+ * fp64, 1 = fp32.  NFT_ERR_ARG for a NULL pointer, ndim outside 2..3, split
+ * outside [1, ndim), nrow < 1, an axis < 1, or strides below the grid size
+ * for nrow > 1. */
+int nft_mirror_mix(const void* x, int64_t x_stride, void* y, int64_t y_stride, int nrow, int ndim,
+                   const int64_t* shape, int split, int dtype, hipStream_t stream);
+/* The amplitude table over the combined bins b = b1 * B2 + b2 (B1, B2 >= 2):
+ *   A[0,0] = z,  A[b1,0] = a1[b1],  A[0,b2] = a2[b2],  A[b1,b2] = a1[b1] a2[b2] / z,
+ *   a_i = s_i m_i (the components' amplitudes m_i of B_i values, entry 0
+ *   ignored),  z = s0 exp(lm_o + ls_o x_zm).
+ * One linearisation is nft_prod_const_size(B1, B2) doubles on the device:
+ * z, z ls_o, a1 / z and a2 / z. */
+int64_t nft_prod_const_size(int64_t B1, int64_t B2);
+/* bytes of VJP workspace per right-hand side */
+size_t nft_prod_workspace(int64_t B1, int64_t B2);
+/* Table and constants at nitem points in one launch: item r reads
+ * m1[r * m1_stride ..], m2[r * m2_stride ..], x_zm[r * lat_stride] and writes
+ * A[r * A_stride ..] and consts[r * const_stride ..].  NFT_ERR_ARG for
+ * B_i < 2, nitem < 1, a NULL pointer, s0 <= 0 or overlapping output rows. */
+int nft_prod_forward(int64_t B1, int64_t B2, const double* m1, int64_t m1_stride, const double* m2,
+                     int64_t m2_stride, const double* x_zm, int64_t lat_stride, double lm_o, double ls_o, double s0,
+                     double s1, double s2, int nitem, double* A, int64_t A_stride, double* consts,
+                     int64_t const_stride, hipStream_t stream);
+/* da[b * nrhs + r] (bin-major, the layout of nft_hartley_fuse.c_estride) for
+ * the components' tangents dm_i[r * dm_i_stride + b_i] and t_zm[r * lat_stride]:
+ *   dA[0,0] = dz,  dA[b1,0] = da1,  dA[0,b2] = da2,
+ *   dA[b1,b2] = da1 (a2/z) + (a1/z) da2 - (a1/z)(a2/z) dz,
+ *   da_i = s_i dm_i,  dz = z ls_o t_zm,
+ * one streaming pass with 16-byte stores; RHS r of a batched call is bitwise
+ * the nrhs = 1 call.  All RHS share the one constant set.  NFT_ERR_ARG for
+ * B_i < 2, nrhs < 1, a NULL pointer or overlapping dm rows. */
+int nft_prod_jvp_batched(int64_t B1, int64_t B2, const double* consts, double s1, double s2, const double* dm1,
+                         int64_t dm1_stride, const double* dm2, int64_t dm2_stride, const double* t_zm,
+                         int64_t lat_stride, double* da, int nrhs, hipStream_t stream);
+/* The transpose, for the bin sums g[r * g_stride + b]: gm1[r * gm1_stride +
+ * b1] and gm2[r * gm2_stride + b2] (the cotangents of m_1, m_2, entry 0 = 0)
+ * and out_zm[r * lat_stride] = shift * d_zm[r * lat_stride] + z ls_o (g[0,0] -
+ * sum_{b1,b2>0} g a1 a2 / z^2)  (d_zm NULL or shift 0: no d term).  Two
+ * launches: 16 x 256 tile partials (wave shuffle trees and LDS) into ws, then
+ * a fold in tile order whose order depends on (B1, B2) alone, so RHS r of a
+ * batched call is bitwise the nrhs = 1 call.  ws: nrhs *
+ * nft_prod_workspace(B1, B2) bytes.  NFT_ERR_ARG as above (B1 <= 16 * 65535). */
+int nft_prod_vjp_batched(int64_t B1, int64_t B2, const double* consts, double s1, double s2, const double* g,
+                         int64_t g_stride, double* gm1, int64_t gm1_stride, double* gm2, int64_t gm2_stride,
+                         double* out_zm, const double* d_zm, int64_t lat_stride, double shift, double* ws, int nrhs,
+                         hipStream_t stream);
 
 /* ---- launch profiler (HIP events) -------------------------------------- */
 /* Between nft_prof_begin and nft_prof_end every hot-path kernel launch

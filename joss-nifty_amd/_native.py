@@ -109,6 +109,15 @@ SIGNATURES = {
     "nft_matern_forward_batched": (_i, [_p, _p, _p, _p, _p, _i64, _i, _p, _i64, _p, _i64, _p, _p]),
     "nft_matern_jvp_batched": (_i, [_p, _p, _i, _p, _i64, _p, _i64, _i64, _i, _i, _p]),
     "nft_matern_vjp_batched": (_i, [_p, _p, _i, _p, _i64, _p, _p, _i64, _d, _p, _i, _p]),
+    # product-spectrum fields: the frame change and the combined-bin table
+    "nft_mirror_mix": (_i, [_p, _i64, _p, _i64, _i, _i, _p, _i, _i, _p]),
+    "nft_prod_const_size": (_i64, [_i64, _i64]),
+    "nft_prod_workspace": (_sz, [_i64, _i64]),
+    "nft_prod_forward": (_i, [_i64, _i64, _p, _i64, _p, _i64, _p, _i64, _d, _d, _d, _d, _d, _i, _p, _i64, _p, _i64,
+                              _p]),
+    "nft_prod_jvp_batched": (_i, [_i64, _i64, _p, _d, _d, _p, _i64, _p, _i64, _p, _i64, _p, _i, _p]),
+    "nft_prod_vjp_batched": (_i, [_i64, _i64, _p, _d, _d, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _d, _p, _i,
+                                  _p]),
 }
 
 
@@ -806,6 +815,21 @@ def samp_adjoint(plan, y, out, colscale=None, rowscale=None, scale=1.0):
                                         dtype_code(y.dtype), float(scale), k, y[0].numel(), out[0].numel(),
                                         stream_ptr()))
     return out
+
+
+def mirror_mix(x, y, shape, split, rows=1, x_stride=0, y_stride=0):
+    """y = R x (nft_mirror_mix) for `rows` grids of `shape`, row r at element
+    r * stride of x / y (tensors whose data_ptr is row 0); y may be x"""
+    lib = load()
+    for t in (x, y):
+        if not t.is_cuda:
+            raise NativeError(f"nifty_amd hot-path ops run on the GPU only (got a {t.device} tensor)")
+    if x.dtype != y.dtype:
+        raise NativeError("mirror_mix: x and y dtypes differ")
+    sh = (ctypes.c_int64 * len(shape))(*shape)
+    _check(lib.nft_mirror_mix(ptr(x), int(x_stride), ptr(y), int(y_stride), int(rows), len(shape), sh, int(split),
+                              dtype_code(x.dtype), stream_ptr()))
+    return y
 
 
 def amp_jvp(const, t_fl, t_sl, t_flex, t_asp, t_zm, t_spec, da):

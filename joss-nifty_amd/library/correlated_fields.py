@@ -232,9 +232,15 @@ class CorrelatedFieldMaker:
     LogNormal, `offset_mean` a scalar or None) returns the fused Matern field
     (`_MaternFieldModel`: the same engine with the closed-form amplitude of
     library/matern.py and the nft_matern_* kernels), and `amplitude` its fused
-    amplitude operator.  Every other case
-    (product spectra, a Matern component beside another one, a unit or
-    operator-valued zero mode, a field offset) is built as the reference's
+    amplitude operator.  TWO `add_fluctuations` components, each on one
+    RGSpace with an RGSpace harmonic partner, at most 3 grid axes in total,
+    with a LogNormal zero mode and `offset_mean` a scalar or None, return the
+    fused product field (`library/product.py`, `_ProductFieldModel`: the same
+    engine on the joint grid in the frame R xi, with the amplitude table over
+    the combined bins and the nft_prod_* / nft_mirror_mix kernels); `amplitude`
+    still raises for it, as in the reference.  Every other case
+    (three or more components, a Matern component beside another one, a unit
+    or operator-valued zero mode, a field offset) is built as the reference's
     operator tree
     (:764-823) on the device operators: per-component fused amplitudes,
     PowerDistributor + ContractionOperator broadcasts, and the native
@@ -336,7 +342,14 @@ class CorrelatedFieldMaker:
     # ------------------------------------------------------------ lowering
     def _fusable(self):
         """One non-parametric or one Matern component on an RGSpace, zero
-        mode off or LogNormal: the cases the fused operators restate exactly."""
+        mode off or LogNormal, or two non-parametric components on RGSpaces of
+        at most 3 grid axes in total with a LogNormal zero mode: the cases the
+        fused operators restate exactly."""
+        if len(self._a) == 2:
+            return (all(hasattr(a, "model") for a in self._a) and self._offset_std is not None
+                    and all(len(t) == 1 and _rg_only(t) for t in self._target_subdomains)
+                    and _rg_only([a.harmonic_partner for a in self._a])
+                    and sum(len(t[0].shape) for t in self._target_subdomains) <= 3)
         if len(self._a) != 1 or not (hasattr(self._a[0], "model") or hasattr(self._a[0], "matern_params")):
             return False
         if not (self._azm is not None and (self._offset_std is not None
@@ -347,6 +360,10 @@ class CorrelatedFieldMaker:
 
     def _fused_model(self, offset_mean):
         from .correlated_fields_simple import _CorrelatedFieldModel, _MaternFieldModel
+        if len(self._a) == 2:
+            from .product import _ProductFieldModel
+            comps = [(t[0], a.harmonic_partner) + tuple(a.params) for t, a in zip(self._target_subdomains, self._a)]
+            return _ProductFieldModel(comps, offset_mean, self._offset_std, self._prefix)
         a = self._a[0]
         if hasattr(a, "matern_params"):
             scale, cutoff, slope, pre, totvol = a.matern_params

@@ -997,7 +997,17 @@ class _FusedFieldBase(Operator):
     / matern._MaternAmplitudeModel): everything but the construction of the
     amplitude.  `xp` prefixes the 'xi' key."""
 
-    def __init__(self, amp, target, harmonic_partner, offset_mean, xp):
+    # the Jacobian class; _xi_frame: xi in the frame the engine works in
+    # (library/product.py rotates it, and its Jacobian keeps R xi)
+    _jacobian = CFJacobian
+    own_frame = False
+
+    def _xi_frame(self, xi):
+        return xi
+
+    def __init__(self, amp, target, harmonic_partner, offset_mean, xp, c_h=None):
+        """target / harmonic_partner: one space each, or (product spectra) the
+        tuples of the sub-spaces with c_h the product of their scalar dvols"""
         self.amp = amp
         self.k_xi = xp + "xi"
         dom = dict(self.amp.domain_dict)
@@ -1005,15 +1015,16 @@ class _FusedFieldBase(Operator):
         self._domain = MultiDomain.make(dom)
         self._target = DomainTuple.make(target)
         self.harmonic_partner = harmonic_partner
-        self.c_h = float(harmonic_partner.scalar_dvol)
+        self.c_h = float(harmonic_partner.scalar_dvol if c_h is None else c_h)
         self.offset_mean = None if offset_mean is None else float(offset_mean)
         self.bins = BinIndex.get(self.amp.pspace.pindex, self.amp.B, config.device())
         # bin sums of the Jacobian adjoint: mirror-folded where the grid allows
         # (rounding-level parity); the value path keeps the bincount order
         self.jbins = BinIndex.get(self.amp.pspace.pindex, self.amp.B, config.device(), fold=True)
         self._layout = None
-        self.amplitude = _AmplitudeOperator(self.amp)
-        self.power_spectrum = _AmplitudeOperator(self.amp, power=2)
+        if isinstance(self.amp.pspace, PowerSpace):  # a product table has no PowerSpace of its own
+            self.amplitude = _AmplitudeOperator(self.amp)
+            self.power_spectrum = _AmplitudeOperator(self.amp, power=2)
 
     @property
     def layout(self):
@@ -1032,12 +1043,13 @@ class _FusedFieldBase(Operator):
         afull = torch.empty(self.harmonic_partner.shape, dtype=a.dtype, device=a.device)
         b = self.bins
         _native.bin_gather(a, b.pindex, afull, 1, b.npix, b.nbin, 1)
+        xi = self._xi_frame(lat[self.k_xi])
         s = _native.hartley_fused(torch.empty_like(afull), range(afull.ndim), self.c_h,
-                                  pro=dict(a=afull, x=lat[self.k_xi].contiguous()),
+                                  pro=dict(a=afull, x=xi.contiguous()),
                                   convention=hartley_convention_code())
         if self.offset_mean is not None:
             s = s + self.offset_mean
-        return s, a, c, afull
+        return s, a, c, afull, xi
 
     def apply(self, x):
         self._check_input(x)
@@ -1047,9 +1059,9 @@ class _FusedFieldBase(Operator):
         hit = self._recall(lat)
         if hit is not None and (not lin or hit[1] is not None):
             return x.new(hit[0], hit[1]) if lin else hit[0]
-        s, a, c, afull = self._value(lat)
+        s, a, c, afull, xi = self._value(lat)
         res = Field(self._target, s)
-        jac = CFJacobian(self, c, a, afull, lat[self.k_xi]) if lin else None
+        jac = self._jacobian(self, c, a, afull, xi) if lin else None
         if lin:
             # the value lives as long as its Jacobian (the operators after the
             # model drop their input's Linearization at once)

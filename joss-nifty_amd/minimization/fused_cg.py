@@ -71,9 +71,7 @@ class _State:
     """Energy-like view of the fused iterate for IterationControllers."""
 
     def __init__(self, value, gnorm, lazy):
-        self._value = value
-        self.gradient_norm = gnorm
-        self._lazy = lazy
+        self._value, self.gradient_norm, self._lazy = value, gnorm, lazy
 
     @property
     def value(self):
@@ -122,28 +120,23 @@ def _capture(fn):
 
 
 def _reads_value(ctl):
-    """False for controllers that never look at the energy value
-    (GradientNormController.check without a name and without an energy
-    history, iteration_controllers.py:188-221).  A subclass may read it in an
-    overridden check, so only the exact class qualifies.  (The decision trace
-    reads values from scalars recorded beside the iteration, whichever runs.)"""
+    """False for controllers that never look at the energy value (GradientNormController.check without a name
+    and without an energy history, iteration_controllers.py:188-221).  A subclass may read it in an overridden
+    check, so only the exact class qualifies.  (The decision trace reads values from scalars recorded beside
+    the iteration, whichever runs.)"""
     from .iteration_controllers import GradientNormController
     return not (type(ctl) is GradientNormController and getattr(ctl, "_name", None) is None
                 and getattr(ctl, "_history", None) is None)
 
 
-# data-space curvature (nifty_amd.h "curvature from the data space"):
-# shift * d.d summed while d is formed, (J d).W(J d) while the LOS forward
-# reduces its lines -- no curvature pass over q and d (NFT_CURV_DATA=0: off)
+# data-space curvature (nifty_amd.h "curvature from the data space"): shift * d.d summed while d is formed,
+# (J d).W(J d) while the LOS forward reduces its lines -- no curvature pass over q and d (NFT_CURV_DATA=0: off)
 CURV_DATA = os.environ.get("NFT_CURV_DATA", "1") != "0"
-# ... also for value-driven controllers (energy deltas, gradient-norm
-# tolerances; NFT_CURV_DATA_VALUE=1, off by default).  Equal in exact
-# arithmetic, the data-space curvature rounds differently from the
-# reference's d.(A d), and alpha = gamma / curv then no longer cancels d.r
-# exactly in r -= alpha q: the CG energies leave the reference's trajectory
-# (DESIGN.md section 1 has the measurement).  Value-driven controllers
-# therefore keep d.q, and with it the separate update pass (the carried
-# update needs alpha before the adjoint).
+# ... also for value-driven controllers (energy deltas, gradient-norm tolerances; NFT_CURV_DATA_VALUE=1, off by
+# default).  Equal in exact arithmetic, the data-space curvature rounds differently from the reference's
+# d.(A d), and alpha = gamma / curv then no longer cancels d.r exactly in r -= alpha q: the CG energies leave
+# the reference's trajectory (DESIGN.md section 1 has the measurement).  Value-driven controllers therefore
+# keep d.q, and with it the separate update pass (the carried update needs alpha before the adjoint).
 CURV_DATA_VALUE = os.environ.get("NFT_CURV_DATA_VALUE", "0") == "1"
 
 
@@ -174,28 +167,34 @@ _COUNT_ONLY_STATE = _CountOnlyState()
 
 # queued CG iterations between host reads (NFT_CG_CHUNK=0: one read per step)
 CHUNK = os.environ.get("NFT_CG_CHUNK", "1") != "0"
-# The grid segment's CG update carried by the adjoint transform's epilogue
-# (data-space curvature: alpha is known before the adjoint): q's grid segment
-# is neither stored nor read back (NFT_CG_CARRY=0: separate update pass)
+# The grid segment's CG update carried by the adjoint transform's epilogue (data-space curvature: alpha is known
+# before the adjoint): q's grid segment is neither stored nor read back (NFT_CG_CARRY=0: separate update pass)
 _CARRY = os.environ.get("NFT_CG_CARRY", "1") != "0"
-# ... and its direction update inside the folded prologue (NFT_CG_CARRY_DIR=0:
-# a separate direction pass)
+# ... and its direction update inside the folded prologue (NFT_CG_CARRY_DIR=0: a separate direction pass)
 _CARRY_DIR = os.environ.get("NFT_CG_CARRY_DIR", "1") != "0"
-# the amplitude keys' direction with the JVP, their update + the finalize with
-# the VJP in the two-phase amplitude kernels (NFT_CG_AMP2=0: separate launches)
+# the amplitude keys' direction with the JVP, their update + the finalize with the VJP in the two-phase
+# amplitude kernels (NFT_CG_AMP2=0: separate launches)
 _AMP2 = os.environ.get("NFT_CG_AMP2", "1") != "0"
-# deferred iterate inside queued chunks of count-only solves
-# (nft_hartley_fuse.lazy_*): the grid segment's directions go to ring slots,
-# x is brought up to date once per chunk (nft_cg_lazy_flush, bitwise the
-# per-step update); NFT_CG_LAZY=0: x updated every step
+# deferred iterate inside queued chunks of count-only solves (nft_hartley_fuse.lazy_*): the grid segment's
+# directions go to ring slots, x is brought up to date once per chunk (nft_cg_lazy_flush, bitwise the per-step
+# update); NFT_CG_LAZY=0: x updated every step
 LAZY = os.environ.get("NFT_CG_LAZY", "1") != "0"
-# compaction of the lock-step batch once right-hand sides stop
-# (NFT_CG_COMPACT=0: frozen rows ride along to the end)
+# compaction of the lock-step batch once right-hand sides stop (NFT_CG_COMPACT=0: frozen rows ride along)
 COMPACT = os.environ.get("NFT_CG_COMPACT", "1") != "0"
 # at most MAX_BATCH right-hand sides per loop (fused_cg_batch_or_none)
 MAX_BATCH = 8
-# which iterations the batched loop ran (tests assert the timed path ran)
+# which iterations the batched loop ran (tests assert the timed path ran) and its frame-hook launches
 STATS = collections.Counter()
+
+
+def _frame(core, hook, *bufs, copy=False):
+    """the packed (k, size) buffers through the core's frame hook (to_frame / from_frame: one batched launch
+    each, counted in STATS["frame_launches"]; on copies if asked); a core without the hook: as they are"""
+    f = getattr(core, hook, None)
+    if f is None:
+        return bufs
+    STATS["frame_launches"] += sum(b is not None for b in bufs)
+    return tuple(b if b is None else f(b.clone() if copy else b) for b in bufs)
 
 
 def _quad_blocks(core, W, dtype, controllers=()):
@@ -743,7 +742,8 @@ class _BatchLoop:
 
                 def lazy(p=p, cache=cache, Xc=X, Rc=Rr):
                     if "v" not in cache:
-                        cache["v"] = (lay.unpack(Xc[p].double()), lay.unpack(Rc[p].double()))
+                        xr_ = _frame(self.core, "from_frame", Xc[p:p + 1].double(), Rc[p:p + 1].double(), copy=True)
+                        cache["v"] = (lay.unpack(xr_[0][0]), lay.unpack(xr_[1][0]))
                     return cache["v"]
                 xr = float(hj[_native.CG_XR])
                 value = 0.5 * (xr - float(hj[_native.CG_XB]))
@@ -853,10 +853,10 @@ class FusedCGBatch(FusedCG):
         self.controllers = controllers
 
     def run(self, energies):
-        k = len(energies)
-        lay, core = self.layout, self.core
+        from .quadratic_energy import QuadraticEnergy
+        lay, core, A = self.layout, self.core, energies[0].metric
         dt = torch.float32 if mixed_precision(core, self.W) else torch.float64
-        X = torch.zeros((k, lay.size), dtype=dt, device=core.device)
+        X = torch.zeros((len(energies), lay.size), dtype=dt, device=core.device)
         Rr = torch.zeros_like(X)
         Bv = torch.zeros_like(X) if energies[0]._b is not None else None
         for j, e in enumerate(energies):
@@ -864,12 +864,12 @@ class FusedCGBatch(FusedCG):
             lay.pack(e.gradient, out=Rr[j])
             if Bv is not None:
                 lay.pack(e._b, out=Bv[j])
-        A = energies[0].metric
+        # a core with a frame of its own (library/product.py) iterates in it
+        _frame(core, "to_frame", X, Rr, Bv)
         X, status = self.run_packed(X, Rr, Bv, energies)
-        from .quadratic_energy import QuadraticEnergy
+        X, Rr = _frame(core, "from_frame", X.double(), Rr.double())
         # (status, moved): moved is None for an energy returned as it came
-        return [(e, st) if moved is None else
-                (QuadraticEnergy(lay.unpack(X[j].double()), A, e._b, _grad=lay.unpack(Rr[j].double())), st)
+        return [(e, st) if moved is None else (QuadraticEnergy(lay.unpack(X[j]), A, e._b, _grad=lay.unpack(Rr[j])), st)
                 for j, (e, (st, moved)) in enumerate(zip(energies, status))]
 
     def run_packed(self, X, Rr, Bv, starts):

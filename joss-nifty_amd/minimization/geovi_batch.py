@@ -398,7 +398,9 @@ class Pipeline:
             ops = [o for op in f_lh for o in (op._ops if isinstance(op, _OpChain) else (op,))]
         else:
             ops = list(f_lh._ops) if isinstance(f_lh, _OpChain) else [f_lh]
-        if not ops or not isinstance(ops[-1], _FusedFieldBase):
+        # a field that works in a frame of its own (library/product.py): the
+        # Jacobian passes here do not know it -- the refinement runs per sample
+        if not ops or not isinstance(ops[-1], _FusedFieldBase) or ops[-1].own_frame:
             return None
         stages = [_CFStage(ops[-1])]
         for op in reversed(ops[:-1]):
