@@ -832,24 +832,6 @@ def mirror_mix(x, y, shape, split, rows=1, x_stride=0, y_stride=0):
     return y
 
 
-def amp_jvp(const, t_fl, t_sl, t_flex, t_asp, t_zm, t_spec, da):
-    """da = J_amp t (constants `const`: AmpConst holding device pointers)."""
-    lib = load()
-    require_device(t_fl, t_sl, t_flex, t_asp, t_zm, t_spec, da)
-    ws = workspace(lib.nft_amp_workspace(const.B), da.device, "amp")
-    _check(lib.nft_amp_jvp(ctypes.byref(const), ptr(t_fl), ptr(t_sl), ptr(t_flex), ptr(t_asp),
-                           ptr(t_zm), ptr(t_spec), ptr(da), ptr(ws), stream_ptr()))
-    return da
-
-
-def amp_vjp(const, g, out):
-    """out (AmpOut of device pointers) = shift * d + J_amp^T g."""
-    lib = load()
-    require_device(g)
-    ws = workspace(lib.nft_amp_workspace(const.B), g.device, "amp")
-    _check(lib.nft_amp_vjp(ctypes.byref(const), ptr(g), ctypes.byref(out), ptr(ws), stream_ptr()))
-
-
 class LaunchProfile:
     """``with LaunchProfile() as p: ...`` -> p.records = [(label, ms), ...] for
     every hot-path kernel launched inside (HIP events on the launch stream)."""

@@ -20,6 +20,7 @@ gather/scatter) and whose B-sized amplitude Jacobian runs in the nft_amp_*
 scan kernels on constants precomputed at the expansion point.  CFJacobian also implements ``sandwich_apply`` /
 ``metric_flat`` so that SandwichOperator and the fused CG can evaluate
 J^T W J without materialising the operator tree."""
+import ctypes
 import os
 import weakref
 
@@ -39,8 +40,10 @@ from ..operators.linear_operator import LinearOperator
 from ..operators.operator import Operator
 from ..packing import PackedLayout
 from ..utilities import lognormal_moments
+from .amplitude_base import DeviceLin, _AmplitudeBase
 from .correlated_fields import (_log_vol, _relative_log_k_lengths, mode_multiplicity, slope_remove,
                                 slope_remove_adjoint, twolog, twolog_adjoint)
+from .matern import _MaternAmplitudeModel
 
 
 # torch formulation of the amplitude JVP/VJP instead of the nft_amp kernels
@@ -72,45 +75,22 @@ _FOLD_R2C = os.environ.get("NFT_FOLD_R2C", "1") != "0"
 # bitwise the same results with fewer scans); tests switch it off for A/B
 AMP2_TABLE = True
 
-class AmpLin:
-    """Linearisation points of the amplitude made on the device
-    (_AmplitudeModel.forward_rows): values a (k, B), the per-row constant
-    vectors (buf) and k device nft_amp_const structs pointing into them.
-    Stands in for the host AmpConst wherever the native JVP/VJP takes one:
-    `host` carries B and the flags for the launch geometry, the kernels read
-    every value from the device structs (item_consts)."""
+
+class AmpLin(DeviceLin):
+    """DeviceLin of _AmplitudeModel.forward_rows: k device nft_amp_const"""
 
     def __init__(self, amp, a, buf, dconst, k):
-        import ctypes
-        self.a, self.buf, self.dconst, self.k = a, buf, dconst, k
-        self.keep = None
-        self.size = ctypes.sizeof(_native.AmpConst)
         h = _native.AmpConst()
         h.B = amp.B
         h.has_flex, h.has_asp, h.has_zm = int(amp.has_flex), int(amp.has_asp), int(amp.has_zm)
-        self.host = h
-        self._rep = {}
-
-    @property
-    def B(self):
-        return self.host.B
-
-    def row_bytes(self, r):
-        return self.dconst[r * self.size:(r + 1) * self.size]
-
-    def items(self, k, row=0):
-        """device pointer of k consecutive structs: row `row` shared by k
-        right-hand sides"""
-        if self.k == 1 and k == 1:
-            return self.dconst.data_ptr()
-        key = (k, row)
-        if key not in self._rep:
-            self._rep[key] = self.row_bytes(row).repeat(k)
-        return self._rep[key].data_ptr()
+        super().__init__(h, a, buf, dconst, k)
 
 
-class _AmplitudeModel:
+class _AmplitudeModel(_AmplitudeBase):
     """Amplitude A(theta) on the PowerSpace, its JVP and VJP (B-sized math)."""
+
+    # the two-phase kernels (nft_amp2_*) take fp32 storage
+    supports_fp32 = True
 
     def __init__(self, target, harmonic_partner, offset_std, fluctuations, flexibility, asperity,
                  loglogavgslope, prefix, zm_prefix=None):
@@ -122,6 +102,8 @@ class _AmplitudeModel:
         self.k_fl, self.k_sl = p + "fluctuations", p + "loglogavgslope"
         self.k_flex, self.k_asp = p + "flexibility", p + "asperity"
         self.k_spec, self.k_zm = p + "spectrum", zp + "zeromode"
+        # the order of the nft_amp key pointers, and of nft_amp_out's fields
+        self.keys = (self.k_fl, self.k_sl, self.k_flex, self.k_asp, self.k_zm, self.k_spec)
         self.has_flex = flexibility is not None
         self.has_asp = asperity is not None
         self.has_zm = offset_std is not None
@@ -299,7 +281,6 @@ class _AmplitudeModel:
         one native pass (nft_amp_forward_batched): at(key) -> device pointer of
         row 0's key or None, rows lat_stride elements apart.  Nothing is read
         back to the host."""
-        import ctypes
         lib = _native.load()
         nbuf = int(lib.nft_amp_forward_buf(self.B))
         a = torch.empty((k, self.B), dtype=torch.float64, device=device)
@@ -313,51 +294,28 @@ class _AmplitudeModel:
             P(buf.data_ptr()), nbuf, P(dconst.data_ptr()), P(ws.data_ptr()), _native.stream_ptr()))
         return AmpLin(self, a, buf, dconst, k)
 
-    def forward_native(self, lat):
-        """forward_rows at one latent point given as a dict key -> tensor"""
-        vals = {kk: v.contiguous() for kk, v in lat.items() if kk in self.domain_dict}
+    def _launch(self, const, item_consts, k, device):
+        """(lib, host, ic, mode, ws) of a native call on k right-hand sides:
+        the library, _item_mode's triple and the shared amplitude workspace"""
+        lib = _native.load()
+        host, ic, mode = self._item_mode(const, item_consts)
+        ws = _native.workspace(k * lib.nft_amp_workspace(self.B), device, "amp")
+        return lib, host, ic, mode, ws
 
-        def at(key):
-            return vals[key].data_ptr() if key in vals else None
-        lin = self.forward_rows(at, 1, 0, next(iter(vals.values())).device)
-        lin.keep = vals
-        return lin
-
-    def _ptrs(self, D, off):
-        """base pointers of the amplitude keys of packed row 0 of D (or None)"""
-        def at(key):
-            if key not in off:
-                return None
-            return D[0, off[key]:].data_ptr()
-        return at
-
-    def _keys6(self):
-        return (self.k_fl, self.k_sl, self.k_flex, self.k_asp, self.k_zm, self.k_spec)
-
-    def _key_ptrs(self, T, off):
-        """ctypes array of the 6 key pointers (fl, sl, flex, asp, zm, spec) of
-        packed row 0 of T (NULL for absent keys), or NULL if T is None"""
-        import ctypes
-        if T is None:
-            return None
-        return (ctypes.c_void_p * 6)(*[T[0, off[kk]:].data_ptr() if kk in off else None for kk in self._keys6()])
-
-    @staticmethod
-    def _item_mode(const, item_consts):
-        """(host AmpConst, item pointer, nft_amp2 item_mode): an AmpLin
-        without per-item constants is ONE device constant set shared by every
-        right-hand side (mode 2)"""
-        if isinstance(const, AmpLin):
-            if item_consts is None:
-                return const.host, const.items(1), 2
-            return const.host, item_consts, 1
-        return const, item_consts, (1 if item_consts else 0)
+    def _amp_out(self, at, atd, shift):
+        """nft_amp_out of the key pointers at(key) (results) and atd(key)
+        (the vectors shift multiplies); None for an absent key"""
+        o = _native.AmpOut()
+        for short, key in zip(("fl", "sl", "flex", "asp", "zm", "spec"), self.keys):
+            setattr(o, short, at(key))
+            setattr(o, "d" + short, atd(key))
+        o.shift = float(shift)
+        return o
 
     def amp2_table(self, const):
         """constant-scan table of the constant set `const` (nft_amp2_prepare),
         made once per set and kept on it; None for per-RHS constant sets, when
         switched off, or when first asked for during a graph capture"""
-        import ctypes
         if not AMP2_TABLE:
             return None
         host, ic, mode = self._item_mode(const, None)
@@ -379,18 +337,14 @@ class _AmplitudeModel:
 
     @staticmethod
     def _tab_ptr(tab):
-        import ctypes
         return ctypes.c_void_p(tab.data_ptr() if tab is not None else None)
 
     def native_jvp_batched(self, const, D, off, da, interleave=False, item_consts=None):
         """da[b] = J_amp D[b] for the k rows of a packed batch D (k, size);
         interleave: da is (B, k), bin-major (one contiguous run per bin)."""
-        import ctypes
         k, size = D.shape
-        lib = _native.load()
-        ws = _native.workspace(k * lib.nft_amp_workspace(self.B), D.device, "amp")
+        lib, host, ic, mode, ws = self._launch(const, item_consts, k, D.device)
         P = ctypes.c_void_p
-        host, ic, mode = self._item_mode(const, item_consts)
         if da.dtype != D.dtype:
             raise _native.NativeError("native_jvp_batched: da and D dtypes differ")
         tab = self.amp2_table(const) if item_consts is None else None
@@ -402,23 +356,18 @@ class _AmplitudeModel:
             return da
         if D.dtype != torch.float64:
             raise _native.NativeError("the multi-kernel amplitude JVP is fp64 only (NFT_AMP2=0 with fp32 storage)")
-        at = self._ptrs(D, off)
         if mode == 2:
             ic = const.items(k)
         _native._check(lib.nft_amp_jvp_batched(
-            ctypes.byref(host), P(ic), P(at(self.k_fl)), P(at(self.k_sl)), P(at(self.k_flex)), P(at(self.k_asp)),
-            P(at(self.k_zm)), P(at(self.k_spec)), P(da.data_ptr()), P(ws.data_ptr()), k, size,
+            ctypes.byref(host), P(ic), *self._key_ptrs(D, off), P(da.data_ptr()), P(ws.data_ptr()), k, size,
             1 if interleave else self.B, k if interleave else 1, _native.stream_ptr()))
         return da
 
     def native_vjp_batched(self, const, g, Q, off, D=None, shift=0.0, item_consts=None):
         """Q[b] amplitude keys = shift * D[b] + J_amp^T g[b]."""
-        import ctypes
         k, size = Q.shape
-        lib = _native.load()
-        ws = _native.workspace(k * lib.nft_amp_workspace(self.B), Q.device, "amp")
+        lib, host, ic, mode, ws = self._launch(const, item_consts, k, Q.device)
         P = ctypes.c_void_p
-        host, ic, mode = self._item_mode(const, item_consts)
         dk = self._key_ptrs(D, off) if (D is not None and shift != 0.0) else None
         if g.dtype != Q.dtype or (D is not None and D.dtype != Q.dtype):
             raise _native.NativeError("native_vjp_batched: g, Q and D dtypes differ")
@@ -433,18 +382,10 @@ class _AmplitudeModel:
             raise _native.NativeError("the multi-kernel amplitude VJP is fp64 only (NFT_AMP2=0 with fp32 storage)")
         if mode == 2:
             ic = const.items(k)
-        atq = self._ptrs(Q, off)
         atd = self._ptrs(D, off) if (D is not None and shift != 0.0) else (lambda key: None)
-        o = _native.AmpOut()
-        for short, key in (("fl", self.k_fl), ("sl", self.k_sl), ("flex", self.k_flex), ("asp", self.k_asp),
-                           ("zm", self.k_zm), ("spec", self.k_spec)):
-            setattr(o, short, atq(key))
-            setattr(o, "d" + short, atd(key))
-        o.shift = float(shift)
-        _native._check(lib.nft_amp_vjp_batched(ctypes.byref(host), ctypes.c_void_p(ic),
-                                               ctypes.c_void_p(g.data_ptr()), ctypes.byref(o),
-                                               ctypes.c_void_p(ws.data_ptr()), k, size, self.B,
-                                               _native.stream_ptr()))
+        o = self._amp_out(self._ptrs(Q, off), atd, shift)
+        _native._check(lib.nft_amp_vjp_batched(ctypes.byref(host), P(ic), P(g.data_ptr()), ctypes.byref(o),
+                                               P(ws.data_ptr()), k, size, self.B, _native.stream_ptr()))
         return Q
 
     # ----- the amplitude keys' CG work carried by the two-phase kernels
@@ -457,12 +398,9 @@ class _AmplitudeModel:
         """d = max(0, gamma/gprev) d + r on the amplitude keys of the k rows of
         D (in place), d.d partials per tile (times shift) into part, and
         da (B, k) = J_amp d, bin-major (nft_amp2_jvp with residual keys)."""
-        import ctypes
         k, size = D.shape
-        lib = _native.load()
-        ws = _native.workspace(k * lib.nft_amp_workspace(self.B), D.device, "amp")
+        lib, host, ic, mode, ws = self._launch(const, None, k, D.device)
         P = ctypes.c_void_p
-        host, ic, mode = self._item_mode(const, None)
         _native._check(lib.nft_amp2_jvp(ctypes.byref(host), P(ic), mode, self._key_ptrs(D, off),
                                         self._key_ptrs(R, off), size, P(da.data_ptr()), 1, k, P(ws.data_ptr()), k,
                                         P(SC.data_ptr()), P(part.data_ptr()), int(pstride), float(shift),
@@ -474,12 +412,9 @@ class _AmplitudeModel:
         """the amplitude keys' CG update x -= alpha d, r -= alpha (J_amp^T g +
         shift d) and the iteration's finalize over their r.r / x.r partials
         and the grid segment's (nft_amp2_vjp with out2)"""
-        import ctypes
         k, size = X.shape
-        lib = _native.load()
-        ws = _native.workspace(k * lib.nft_amp_workspace(self.B), X.device, "amp")
+        lib, host, ic, mode, ws = self._launch(const, None, k, X.device)
         P = ctypes.c_void_p
-        host, ic, mode = self._item_mode(const, None)
         _native._check(lib.nft_amp2_vjp(ctypes.byref(host), P(ic), mode, P(g.data_ptr()), self.B,
                                         self._key_ptrs(X, off), self._key_ptrs(R, off), self._key_ptrs(D, off), size,
                                         float(shift), P(ws.data_ptr()), k, P(SC.data_ptr()), P(part.data_ptr()),
@@ -487,48 +422,26 @@ class _AmplitudeModel:
                                         _native.dtype_code(X.dtype), self._tab_ptr(self.amp2_table(const)),
                                         _native.stream_ptr()))
 
+    # single point, dicts key -> contiguous device tensor: the batched entry
+    # points with one right-hand side (what nft_amp_jvp / nft_amp_vjp are in C)
     def native_jvp(self, const, t, da):
-        if isinstance(const, AmpLin):
-            import ctypes
-            lib = _native.load()
-            ws = _native.workspace(lib.nft_amp_workspace(self.B), da.device, "amp")
-            P = ctypes.c_void_p
-
-            def ptr(key):
-                v = t.get(key)
-                return P(v.data_ptr() if v is not None else None)
-            _native.require_device(da, *[v for v in t.values()])
-            _native._check(lib.nft_amp_jvp_batched(
-                ctypes.byref(const.host), P(const.items(1)), ptr(self.k_fl), ptr(self.k_sl), ptr(self.k_flex),
-                ptr(self.k_asp), ptr(self.k_zm), ptr(self.k_spec), P(da.data_ptr()), P(ws.data_ptr()), 1, 0, 0, 1,
-                _native.stream_ptr()))
-            return da
-        g = t.get
-        _native.amp_jvp(const, g(self.k_fl), g(self.k_sl), g(self.k_flex), g(self.k_asp),
-                        g(self.k_zm), g(self.k_spec), da)
+        _native.require_device(da, *[t.get(kk) for kk in self.keys])
+        lib, host, ic, _, ws = self._launch(const, None, 1, da.device)
+        P = ctypes.c_void_p
+        _native._check(lib.nft_amp_jvp_batched(ctypes.byref(host), P(ic), *self._dict_ptrs(t), P(da.data_ptr()),
+                                               P(ws.data_ptr()), 1, 0, 0, 1, _native.stream_ptr()))
         return da
 
     def native_vjp(self, const, g, out, d=None, shift=0.0):
         """out/d: dict key -> contiguous device tensors; out = shift*d + J^T g."""
-        o = _native.AmpOut()
-        names = (("fl", self.k_fl), ("sl", self.k_sl), ("flex", self.k_flex), ("asp", self.k_asp),
-                 ("zm", self.k_zm), ("spec", self.k_spec))
-        for short, key in names:
-            if key in out:
-                setattr(o, short, out[key].data_ptr())
-                if d is not None and shift != 0.0:
-                    setattr(o, "d" + short, d[key].data_ptr())
-        o.shift = float(shift)
-        if isinstance(const, AmpLin):
-            import ctypes
-            lib = _native.load()
-            ws = _native.workspace(lib.nft_amp_workspace(self.B), g.device, "amp")
-            _native.require_device(g)
-            _native._check(lib.nft_amp_vjp_batched(
-                ctypes.byref(const.host), ctypes.c_void_p(const.items(1)), ctypes.c_void_p(g.data_ptr()),
-                ctypes.byref(o), ctypes.c_void_p(ws.data_ptr()), 1, 0, 0, _native.stream_ptr()))
-            return out
-        _native.amp_vjp(const, g, o)
+        _native.require_device(g)
+        lib, host, ic, _, ws = self._launch(const, None, 1, g.device)
+        P = ctypes.c_void_p
+        use_d = d is not None and shift != 0.0
+        o = self._amp_out(lambda key: out[key].data_ptr() if key in out else None,
+                          lambda key: d[key].data_ptr() if use_d and key in out else None, shift)
+        _native._check(lib.nft_amp_vjp_batched(ctypes.byref(host), P(ic), P(g.data_ptr()), ctypes.byref(o),
+                                               P(ws.data_ptr()), 1, 0, 0, _native.stream_ptr()))
         return out
 
 
@@ -599,7 +512,7 @@ class CFJacobian(LinearOperator):
             self._m.amp.amp2_table(self._k[0])  # before any graph capture uses it
         return self._k[0]
 
-    def _times_t(self, t):
+    def _times_frame(self, t):
         """t: dict key->tensor tangent.  Returns position-space grid tensor:
         c_h HT[A_full * t_xi + xi0 * dA[pindex]] in one fused native transform
         (the gather and the two products run inside its first pass)."""
@@ -624,7 +537,7 @@ class CFJacobian(LinearOperator):
             return dict(c=da, index=jb.fold["pindex"], fold=True)
         return dict(c=da, index=self._m.bins.pindex)
 
-    def _adjoint_t(self, g, out=None, d=None, shift=0.0):
+    def _adjoint_frame(self, g, out=None, d=None, shift=0.0):
         """g: grid tensor.  Returns dict key->tensor, or fills the `out` views
         with shift * d + J^T g.  One fused transform produces both
         A_full * v (+ shift * d_xi) and xi0 * v, v = c_h HT g."""
@@ -672,6 +585,17 @@ class CFJacobian(LinearOperator):
         else:
             m.amp.native_vjp(self._const(), ga, out, d, shift)
         return out
+
+    # The operator interface (apply, sandwich_apply, lowering) goes through
+    # _times_t / _adjoint_t, in the latent domain's natural frame; metric_flat
+    # and the packed-buffer methods work in the engine's frame (_times_frame /
+    # _adjoint_frame).  The two differ only for a field with a frame of its
+    # own (library/product.py), which overrides the natural-frame pair.
+    def _times_t(self, t):
+        return self._times_frame(t)
+
+    def _adjoint_t(self, g, out=None, d=None, shift=0.0):
+        return self._adjoint_frame(g, out, d, shift)
 
     def apply(self, x, mode):
         self._check_input(x, mode)
@@ -770,8 +694,7 @@ class CFJacobian(LinearOperator):
         m = self._m
         k = D.shape[0]
         da = self._mv_bufs(k, D.dtype)["da"]
-        m.amp.native_jvp_batched(self._const(), D, dict(zip(self.layout.keys, self.layout.offsets)), da,
-                                 interleave=True)
+        m.amp.native_jvp_batched(self._const(), D, self.layout.key_offsets, da, interleave=True)
         return da
 
     def amp2_tiles(self, k):
@@ -785,7 +708,7 @@ class CFJacobian(LinearOperator):
         m = self._m
         k = D.shape[0]
         da = self._mv_bufs(k, D.dtype)["da"]
-        return m.amp.native_jvp_dir(self._const(), D, R, dict(zip(self.layout.keys, self.layout.offsets)), da, SC,
+        return m.amp.native_jvp_dir(self._const(), D, R, self.layout.key_offsets, da, SC,
                                     part, pstride, shift)
 
     def mv_amp_vjp_cg(self, X, R, D, w, SC, part, pstride, gpart, gp_stride, gp_row, ngp, shift):
@@ -795,7 +718,7 @@ class CFJacobian(LinearOperator):
         k = X.shape[0]
         ga = self._mv_bufs(k, X.dtype)["ga"]
         m.jbins.scatter_from(self.mv_fold(w), ga, k)
-        m.amp.native_vjp_cg(self._const(), ga, X, R, D, dict(zip(self.layout.keys, self.layout.offsets)), SC, part,
+        m.amp.native_vjp_cg(self._const(), ga, X, R, D, self.layout.key_offsets, SC, part,
                             pstride, gpart, gp_stride, gp_row, ngp, shift)
 
     def cg_blocks(self, k):
@@ -850,7 +773,7 @@ class CFJacobian(LinearOperator):
         W = self._weight(W, D.dtype)
         grid = tuple(afull.shape)
         N = afull.numel()
-        xo = dict(zip(lay.keys, lay.offsets))[m.k_xi]
+        xo = lay.key_offsets[m.k_xi]
         axes = tuple(range(1, 1 + len(grid)))
         conv = hartley_convention_code()
         s = bufs["s"]
@@ -902,7 +825,7 @@ class CFJacobian(LinearOperator):
         k = Q.shape[0]
         ga = self._mv_bufs(k, Q.dtype)["ga"]
         m.jbins.scatter_from(self.mv_fold(w) if folded is None else folded, ga, k)
-        m.amp.native_vjp_batched(self._const(), ga, Q, dict(zip(self.layout.keys, self.layout.offsets)), D, shift)
+        m.amp.native_vjp_batched(self._const(), ga, Q, self.layout.key_offsets, D, shift)
         return Q
 
     def grid_segment(self):
@@ -918,7 +841,7 @@ class CFJacobian(LinearOperator):
     def supports_fp32(self):
         """fp32 CG storage (config.set_cg_precision): where the amplitude's
         kernels take it; a solve with another amplitude stays fp64"""
-        return getattr(self._m.amp, "supports_fp32", True)
+        return self._m.amp.supports_fp32
 
     def _metric_flat_batch32(self, D, Q, W, shift):
         """metric_flat_batch on fp32 storage (config.set_cg_precision("fp32")):
@@ -932,14 +855,12 @@ class CFJacobian(LinearOperator):
         B = amp.B
         grid = tuple(self._afull.shape)
         N = self._afull.numel()
-        off = dict(zip(lay.keys, lay.offsets))
+        off = lay.key_offsets
         xo = off[m.k_xi]
         axes = tuple(range(1, 1 + len(grid)))
         conv = hartley_convention_code()
         const = self._const()
-        c32 = getattr(self, "_c32", None)
-        if c32 is None:
-            c32 = self._c32 = dict(afull=self._afull.float(), xi0=self._xi0.float(), W={})
+        afull32, xi032 = self._grid_ops(torch.float32)
         segs = [(o, n) for kk, o, n in zip(lay.keys, lay.offsets, lay.sizes) if kk != m.k_xi]
         D64 = torch.zeros((k, size), dtype=torch.float64, device=D.device)
         for o, n in segs:
@@ -948,22 +869,16 @@ class CFJacobian(LinearOperator):
         amp.native_jvp_batched(const, D64, off, da, interleave=True)
         da32 = da.float()
         s = torch.empty((k,) + grid, dtype=torch.float32, device=self.device)
-        pro = dict(a=c32["afull"], x=D[0, xo:], b=c32["xi0"], **self._pro_bins(da32, k))
+        pro = dict(a=afull32, x=D[0, xo:], b=xi032, **self._pro_bins(da32, k))
         _native.hartley_fused(s, axes, m.c_h, pro=pro, convention=conv, shape=s.shape,
                               batch=dict(period=N, x=size, c=1, c_elem=k))
         if callable(W):
             g = W(s)
         else:
-            if torch.is_tensor(W):
-                key = W.data_ptr()
-                if key not in c32["W"]:
-                    c32["W"][key] = W.float()
-                g = s * c32["W"][key]
-            else:
-                g = s * float(W)
+            g = s * (self._weight(W, torch.float32) if torch.is_tensor(W) else float(W))
         g = g.contiguous()
         w = torch.empty((k,) + grid, dtype=torch.float32, device=self.device)
-        epi = dict(a=c32["afull"], b=c32["xi0"], out2=w)
+        epi = dict(a=afull32, b=xi032, out2=w)
         bt = dict(period=N, out=size, out2=N)
         if shift != 0.0:
             epi.update(d=D[0, xo:], shift=shift)
@@ -981,21 +896,20 @@ class CFJacobian(LinearOperator):
     supports_quad = True
 
     def metric_flat(self, d, q, W, shift, qpart=None):
-        """q = shift * d + J^T W J d on packed latent buffers (fused CG).
-        qpart: partials of the quadratic form (J d).W(J d), from a middle W
-        that supports it (W.quad_blocks)."""
+        """q = shift * d + J^T W J d on packed latent buffers in the engine's
+        frame (fused CG).  qpart: partials of the quadratic form
+        (J d).W(J d), from a middle W that supports it (W.quad_blocks)."""
         lay = self.layout
         dv = lay.views(d)
-        s = self._times_t(dv)
+        s = self._times_frame(dv)
         g = (W(s, qpart=qpart) if qpart is not None else W(s)) if callable(W) else s * W
-        self._adjoint_t(g, lay.views(q), dv, shift)
+        self._adjoint_frame(g, lay.views(q), dv, shift)
 
 
 class _FusedFieldBase(Operator):
     """The fused correlated field  s = offset_mean + c_h HT[A[pindex] * xi]
-    for an amplitude model `amp` (the duck-typed interface of _AmplitudeModel
-    / matern._MaternAmplitudeModel): everything but the construction of the
-    amplitude.  `xp` prefixes the 'xi' key."""
+    for an amplitude model `amp` (an amplitude_base._AmplitudeBase):
+    everything but the construction of the amplitude.  `xp` prefixes the 'xi' key."""
 
     # the Jacobian class; _xi_frame: xi in the frame the engine works in
     # (library/product.py rotates it, and its Jacobian keeps R xi)
@@ -1122,7 +1036,6 @@ class _MaternFieldModel(_FusedFieldBase):
 
     def __init__(self, target, harmonic_partner, offset_mean, offset_std, scale, cutoff, loglogslope,
                  total_volume, prefix, xi_prefix=None):
-        from .matern import _MaternAmplitudeModel
         xp = prefix if xi_prefix is None else xi_prefix
         amp = _MaternAmplitudeModel(harmonic_partner, offset_std, scale, cutoff, loglogslope, total_volume,
                                     prefix, zm_prefix=xp)

@@ -18,10 +18,10 @@ vector finished at the linearisation point:
     dA_b/dxi_loglogslope = (sig_l / 4) A_b log1p(u_b)
     dA_0/dxi_zeromode    = V zm ls_o
 
-_MaternAmplitudeModel has the interface of
-correlated_fields_simple._AmplitudeModel (the `amp` of the fused field,
-CFJacobian and geovi_batch._CFStage); its native passes are the nft_matern_*
-kernels (csrc/nft_matern.hip): one streaming pass for the JVP, three dot
+_MaternAmplitudeModel is an amplitude_base._AmplitudeBase (the `amp` of the
+fused field, CFJacobian and geovi_batch._CFStage), as
+correlated_fields_simple._AmplitudeModel is; its native passes are the
+nft_matern_* kernels (csrc/nft_matern.hip): one streaming pass for the JVP, three dot
 products for the VJP, no scans and no device-global state.  It has no
 two-phase (amp2) form, so the carried CG iteration treats its keys as plain
 segments (fused_cg._CarrySeg) and the solve storage stays fp64."""
@@ -34,53 +34,32 @@ from .. import _native, config
 from ..domain_tuple import DomainTuple
 from ..domains import PowerSpace
 from ..utilities import lognormal_moments
+from .amplitude_base import DeviceLin, _AmplitudeBase
 
 
 def _t(a):
     return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=config.device())
 
 
-class MaternLin:
-    """Linearisation points made on the device (forward_rows): values a
-    (k, B), the finished columns (buf) and k device nft_matern_const structs
-    pointing into them; `host` carries B and has_zm for the launch geometry."""
+class MaternLin(DeviceLin):
+    """DeviceLin of _MaternAmplitudeModel.forward_rows: k device
+    nft_matern_const (buf: the finished columns)"""
 
     def __init__(self, amp, a, buf, dconst, k):
-        self.a, self.buf, self.dconst, self.k = a, buf, dconst, k
-        self.keep = None
-        self.size = ctypes.sizeof(_native.MaternConst)
         h = _native.MaternConst()
         h.B, h.has_zm = amp.B, int(amp.has_zm)
-        self.host = h
-        self._rep = {}
-
-    @property
-    def B(self):
-        return self.host.B
-
-    def row_bytes(self, r):
-        return self.dconst[r * self.size:(r + 1) * self.size]
-
-    def items(self, k, row=0):
-        """device pointer of k consecutive structs: row `row` shared by k
-        right-hand sides"""
-        if self.k == 1 and k == 1:
-            return self.dconst.data_ptr()
-        key = (k, row)
-        if key not in self._rep:
-            self._rep[key] = self.row_bytes(row).repeat(k)
-        return self._rep[key].data_ptr()
+        super().__init__(h, a, buf, dconst, k)
 
 
-class _MaternAmplitudeModel:
+class _MaternAmplitudeModel(_AmplitudeBase):
     """A(scale, cutoff, loglogslope[, zeromode]) on the PowerSpace, its JVP
     and VJP.  scale / cutoff: (mean, std) of LognormalTransforms, loglogslope:
     (mean, std) of a NormalTransform, offset_std: (mean, std) of the LogNormal
     zero mode or None; total_volume: the reference's `totvol`."""
 
-    # the nft_matern kernels are fp64; a solve with this amplitude keeps fp64
-    # storage under config.set_cg_precision("fp32")
-    supports_fp32 = False
+    # the nft_matern kernels are fp64 and have no two-phase (amp2) form: the
+    # base's defaults hold (fp64 storage under config.set_cg_precision("fp32"),
+    # the 'seg' flavour of the carried iteration)
 
     def __init__(self, harmonic_partner, offset_std, scale, cutoff, loglogslope, total_volume, prefix,
                  zm_prefix=None):
@@ -92,6 +71,7 @@ class _MaternAmplitudeModel:
         zp = prefix if zm_prefix is None else zm_prefix
         self.k_scale, self.k_cutoff, self.k_slope = prefix + "scale", prefix + "cutoff", prefix + "loglogslope"
         self.k_zm = zp + "zeromode"
+        self.keys = (self.k_scale, self.k_cutoff, self.k_slope, self.k_zm)   # nft_matern's pointer order
         self.has_zm = offset_std is not None
         self.lm_s, self.ls_s = (float(v) for v in lognormal_moments(*scale))
         self.lm_c, self.ls_c = (float(v) for v in lognormal_moments(*cutoff))
@@ -103,9 +83,6 @@ class _MaternAmplitudeModel:
         if self.has_zm:
             dom[self.k_zm] = DomainTuple.scalar_domain()
         self.domain_dict = dom
-
-    def _keys4(self):
-        return (self.k_scale, self.k_cutoff, self.k_slope, self.k_zm)
 
     # ------------------------------------------------ torch restatement
     def forward(self, lat):
@@ -191,47 +168,6 @@ class _MaternAmplitudeModel:
             P(dconst.data_ptr()), _native.stream_ptr()))
         return MaternLin(self, a, buf, dconst, k)
 
-    def forward_native(self, lat):
-        """forward_rows at one latent point given as a dict key -> tensor"""
-        vals = {kk: v.contiguous() for kk, v in lat.items() if kk in self.domain_dict}
-        _native.require_device(*vals.values())
-
-        def at(key):
-            return vals[key].data_ptr() if key in vals else None
-        lin = self.forward_rows(at, 1, 0, next(iter(vals.values())).device)
-        lin.keep = vals
-        return lin
-
-    def _ptrs(self, D, off):
-        """base pointers of the amplitude keys of packed row 0 of D (or None)"""
-        def at(key):
-            if key not in off:
-                return None
-            return D[0, off[key]:].data_ptr()
-        return at
-
-    def _key_ptrs(self, T, off):
-        """ctypes array of the 4 key pointers of packed row 0 of T (NULL for an
-        absent zero mode), or NULL if T is None"""
-        if T is None:
-            return None
-        return (ctypes.c_void_p * 4)(*[T[0, off[kk]:].data_ptr() if kk in off else None for kk in self._keys4()])
-
-    def _dict_ptrs(self, d):
-        if d is None:
-            return None
-        return (ctypes.c_void_p * 4)(*[d[kk].data_ptr() if kk in d else None for kk in self._keys4()])
-
-    @staticmethod
-    def _item_mode(const, item_consts):
-        """(host constant set, item pointer, item_mode): a MaternLin without
-        per-item constants is ONE device set shared by every right-hand side"""
-        if isinstance(const, MaternLin):
-            if item_consts is None:
-                return const.host, const.items(1), 2
-            return const.host, item_consts, 1
-        return const, item_consts, (1 if item_consts else 0)
-
     def _jvp(self, const, item_consts, t, lat_stride, da, da_stride, da_elem_stride, k):
         host, ic, mode = self._item_mode(const, item_consts)
         P = ctypes.c_void_p
@@ -283,10 +219,3 @@ class _MaternAmplitudeModel:
         self._vjp(const, None, g, 0, self._dict_ptrs(out), self._dict_ptrs(d) if use_d else None, 0,
                   shift if use_d else 0.0, 1)
         return out
-
-    # no two-phase (amp2) form: the carried iteration runs the 'seg' flavour
-    def amp2_table(self, const):
-        return None
-
-    def amp2_tiles(self, const, k):
-        return 0

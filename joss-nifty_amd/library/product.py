@@ -38,6 +38,7 @@ import torch
 from .. import _native
 from ..domain_tuple import DomainTuple
 from ..utilities import lognormal_moments
+from .amplitude_base import _AmplitudeBase
 from .correlated_fields_simple import CFJacobian, _AmplitudeModel, _FusedFieldBase
 
 _P = ctypes.c_void_p
@@ -61,16 +62,17 @@ class ProdLin:
         self.c1, self.c2, self.a, self.cb, self.keep = c1, c2, a, cb, keep
 
 
-class _ProductAmplitudeModel:
-    """A(theta_1, theta_2, zeromode) over the combined bins, its JVP and VJP:
-    the amplitude interface of correlated_fields_simple._AmplitudeModel /
-    matern._MaternAmplitudeModel.  comps: per component (sub-space, harmonic
-    partner, fluctuations, flexibility, asperity, loglogavgslope, key prefix);
+class _ProductAmplitudeModel(_AmplitudeBase):
+    """A(theta_1, theta_2, zeromode) over the combined bins, its JVP and VJP
+    (an amplitude_base._AmplitudeBase whose native passes take the keys from
+    its two components, so it sets no `keys` of its own).  comps: per
+    component (sub-space, harmonic partner, fluctuations, flexibility,
+    asperity, loglogavgslope, key prefix);
     offset_std: (mean, std) of the LogNormal zero mode keyed `zm_prefix`zeromode."""
 
-    # the nft_prod kernels are fp64; a solve with this amplitude keeps fp64
-    # storage under config.set_cg_precision("fp32")
-    supports_fp32 = False
+    # the nft_prod kernels are fp64: the base's supports_fp32 = False holds (a
+    # solve with this amplitude keeps fp64 storage under
+    # config.set_cg_precision("fp32"))
 
     def __init__(self, comps, offset_std, zm_prefix):
         self.parts = tuple(_AmplitudeModel(t, h, None, fl, flex, asp, sl, pre) for t, h, fl, flex, asp, sl, pre in comps)
@@ -251,17 +253,15 @@ class _ProductAmplitudeModel:
             m.amp2_table(c)
         return None
 
-    def amp2_tiles(self, const, k):
-        return 0
-
 
 class ProductJacobian(CFJacobian):
     """CFJacobian of the product field; its xi0 slot holds R xi.  The operator
-    interface (_times_t, _adjoint_t, apply, sandwich_apply) is in the natural
-    frame: the xi tangent is mixed on the way in, the xi cotangent on the way
-    out.  The packed-buffer methods fused_cg calls (metric_flat(_batch), mv_*)
-    work on buffers in the rotated frame, which to_frame / from_frame enter
-    and leave with one batched launch each."""
+    interface (_times_t, _adjoint_t, apply, sandwich_apply, lowering) is in
+    the natural frame: the xi tangent is mixed on the way in, the xi cotangent
+    on the way out.  The packed-buffer methods fused_cg calls
+    (metric_flat(_batch), mv_*) are the base's: they work on buffers in the
+    rotated frame, which to_frame / from_frame enter and leave with one
+    batched launch each."""
 
     def _mix(self, x):
         m = self._m
@@ -270,14 +270,16 @@ class ProductJacobian(CFJacobian):
     def _times_t(self, t):
         t = dict(t)
         t[self._m.k_xi] = self._mix(t[self._m.k_xi].contiguous())
-        return CFJacobian._times_t(self, t)
+        return self._times_frame(t)
 
     def _adjoint_t(self, g, out=None, d=None, shift=0.0):
         k_xi = self._m.k_xi
-        res = CFJacobian._adjoint_t(self, g)
+        res = self._adjoint_frame(g)
         res[k_xi] = self._mix(res[k_xi])
         if out is None:
             return res
+        # a lowered metric (lowering.py: the per-sample geoVI refinement of this
+        # field) asks for the natural-frame adjoint into packed views
         for k, r in res.items():
             if shift != 0.0:
                 torch.add(r.reshape(out[k].shape), d[k], alpha=shift, out=out[k])
@@ -285,20 +287,12 @@ class ProductJacobian(CFJacobian):
                 out[k].copy_(r.reshape(out[k].shape))
         return out
 
-    def metric_flat(self, d, q, W, shift, qpart=None):
-        """q = shift * d + J^T W J d on packed buffers in the rotated frame"""
-        lay = self.layout
-        dv = lay.views(d)
-        s = CFJacobian._times_t(self, dv)
-        g = (W(s, qpart=qpart) if qpart is not None else W(s)) if callable(W) else s * W
-        CFJacobian._adjoint_t(self, g, lay.views(q), dv, shift)
-
     def to_frame(self, buf):
         """the xi segment of every row of the packed (k, size) buffer `buf`
         times R, in place, one launch (R is an involution: from_frame is the
         same map)"""
         m = self._m
-        xo = dict(zip(self.layout.keys, self.layout.offsets))[m.k_xi]
+        xo = self.layout.key_offsets[m.k_xi]
         k, size = buf.shape
         _native.mirror_mix(buf[0, xo:], buf[0, xo:], m.grid, m.split, rows=k, x_stride=size, y_stride=size)
         return buf

@@ -94,18 +94,8 @@ def _pairdots(pairs):
 
 
 # ------------------------------------------------------------------ stages
+from ..library.amplitude_base import DeviceLin  # noqa: E402
 from ..library.correlated_fields_simple import _O2_PAIRS, _PRO_FOLD  # noqa: E402
-
-
-def _items(st, k):
-    """device nft_amp_const array for k right-hand sides: the state's own rows,
-    or its single linearisation point shared by all k"""
-    if st["k"] != 1 or k == 1:
-        return st["dconst"].data_ptr()
-    rep = st.setdefault("rep", {})
-    if k not in rep:
-        rep[k] = st["dconst"].repeat(k)
-    return rep[k].data_ptr()
 
 
 class _CFStage:
@@ -115,7 +105,7 @@ class _CFStage:
     def __init__(self, model):
         self.m = model
         self.lay = model.layout
-        self.off = dict(zip(self.lay.keys, self.lay.offsets))
+        self.off = self.lay.key_offsets
         self.grid = tuple(model.harmonic_partner.shape)
         self.N = int(np.prod(self.grid))
         self.axes = tuple(range(1, 1 + len(self.grid)))
@@ -142,20 +132,23 @@ class _CFStage:
                               batch=dict(period=self.N, x=X.shape[1], a=self.N))
         if m.offset_mean is not None:
             s.add_(m.offset_mean)
-        return s, dict(afull=afull, X=X, lin=lin, lins=[lin], dconst=lin.dconst, k=k)
+        return s, dict(afull=afull, X=X, lin=lin)
 
     @staticmethod
     def stack(states):
         """one batch state from per-sample (state, row) pairs"""
-        if len(states) == 1 and states[0][0]["k"] == 1:
-            return states[0][0]
-        if all(st is states[0][0] for st, _ in states) and [r for _, r in states] == list(range(states[0][0]["k"])):
-            return states[0][0]
+        first = states[0][0]
+        if len(states) == 1 and first["lin"].k == 1:
+            return first
+        if all(st is first for st, _ in states) and [r for _, r in states] == list(range(first["lin"].k)):
+            return first
         afull = torch.stack([st["afull"][r] for st, r in states])
         X = torch.stack([st["X"][r] for st, r in states])
+        # the rows' device structs side by side; their constant vectors stay
+        # where they are, kept alive by the linearisations they belong to
         dconst = torch.cat([st["lin"].row_bytes(r) for st, r in states])
-        lins = [ln for st, _ in states for ln in st["lins"]]
-        return dict(afull=afull, X=X, lin=states[0][0]["lin"], lins=lins, dconst=dconst, k=len(states))
+        lin = DeviceLin(first["lin"].host, None, None, dconst, len(states), keep=[st["lin"] for st, _ in states])
+        return dict(afull=afull, X=X, lin=lin)
 
     def jvp(self, st, V):
         """(k, grid) = J_cf(x_b) V[b]; st shared (k = 1) or per item"""
@@ -164,16 +157,16 @@ class _CFStage:
         k, size = V.shape
         B = m.amp.B
         N = self.N
-        shared = st["k"] == 1
+        shared = st["lin"].k == 1
         out = torch.empty((k,) + self.grid, dtype=V.dtype, device=V.device)
         Xs = st["X"]
         if shared:
             da = torch.empty((B, k), dtype=torch.float64, device=V.device)
-            m.amp.native_jvp_batched(st["lin"], V, self.off, da, interleave=True, item_consts=_items(st, k))
+            m.amp.native_jvp_batched(st["lin"], V, self.off, da, interleave=True, item_consts=st["lin"].per_item(k))
             batch = dict(period=N, x=size, c=1, c_elem=k)
         else:
             da = torch.empty((k, B), dtype=torch.float64, device=V.device)
-            m.amp.native_jvp_batched(st["lin"], V, self.off, da, item_consts=_items(st, k))
+            m.amp.native_jvp_batched(st["lin"], V, self.off, da, item_consts=st["lin"].per_item(k))
             batch = dict(period=N, x=size, c=B, a=N, b=Xs.shape[1])
         pro = dict(a=st["afull"], x=V[0, self.xo:], b=Xs[0, self.xo:], c=da, index=m.bins.pindex)
         jb = m.jbins
@@ -192,7 +185,7 @@ class _CFStage:
         k = G.shape[0]
         size = Q.shape[1]
         N = self.N
-        shared = st["k"] == 1
+        shared = st["lin"].k == 1
         Xs = st["X"]
         # xi0 * v as point-mirror pair sums on the half grid where the CF
         # Jacobian's own adjoint uses them (CFJacobian._pairs)
@@ -216,7 +209,7 @@ class _CFStage:
         else:
             m.jbins.scatter(w, ga, k)
         m.amp.native_vjp_batched(st["lin"], ga, Q, self.off, D=d, shift=shift if d is not None else 0.0,
-                                 item_consts=_items(st, k))
+                                 item_consts=st["lin"].per_item(k))
         return Q
 
 

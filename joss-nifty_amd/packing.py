@@ -34,6 +34,8 @@ class PackedLayout:
             self.sizes.append(n)
             off += (n + ALIGN - 1) // ALIGN * ALIGN
         self.size = max(off, ALIGN)
+        # key -> offset of its segment (fixed with the layout)
+        self.key_offsets = dict(zip(self.keys, self.offsets))
 
     def empty(self):
         return torch.zeros(self.size, dtype=self.dtype, device=self.device)

@@ -108,6 +108,59 @@ def test_amp2_jvp_vjp(ift, restore, shape, args, k):
             Q1 = torch.zeros_like(D[j:j + 1])
             amp.native_vjp_batched(cst, g[j:j + 1], Q1, off, D[j:j + 1], 0.75)
             assert torch.equal(Q1[0], res[1, name][1][j]), (name, j)
+    # the single-point native_jvp / native_vjp (dicts of tensors) are the
+    # ten-kernel batched entry points with one right-hand side: bitwise, for a
+    # host constant set and a device AmpLin
+    if k == 1 and shape in ((6, 5), (96, 96)):
+        _toggle(0)
+        t0 = {kk: lay.views(D[0])[kk] for kk in keys}
+        for name, cst in (("host", const), ("lin", lin)):
+            dab = torch.empty((1, B), dtype=torch.float64, device=dev)
+            amp.native_jvp_batched(cst, D, off, dab)
+            das = amp.native_jvp(cst, t0, torch.empty(B, dtype=torch.float64, device=dev))
+            assert torch.equal(das, dab[0]), name
+            Qb = torch.zeros_like(D)
+            amp.native_vjp_batched(cst, g, Qb, off, D, 0.75)
+            outs = {kk: torch.zeros_like(t0[kk]) for kk in keys}
+            amp.native_vjp(cst, g[0], outs, t0, 0.75)
+            for kk in keys:
+                assert torch.equal(outs[kk], lay.views(Qb[0])[kk]), (name, kk)
+
+
+def test_fp32_fallback_sees_weight_updated_in_place(ift, restore):
+    """metric_flat_batch on fp32 storage without the two-phase kernels
+    (_metric_flat_batch32) keeps no stale fp32 copy of a tensor weight: after
+    W.mul_(2.) the same Jacobian object gives bitwise what a fresh
+    linearisation at the same point gives for the doubled weight"""
+    from nifty_amd.packing import PackedLayout
+    cf = ift.SimpleCorrelatedField(ift.RGSpace((16, 16)), **CF_ARGS)
+    with ift.random.Context(41):
+        pos = 0.1 * ift.from_random(cf.domain, "normal")
+        rows = [ift.from_random(cf.domain, "normal") for _ in range(2)]
+    lay = PackedLayout(cf.domain)
+    D = torch.stack([lay.pack(r) for r in rows]).float()
+    W = torch.rand((16, 16), dtype=torch.float64, device=D.device,
+                   generator=torch.Generator(device=D.device).manual_seed(41)) + 0.5
+    _toggle(0)
+
+    def metric(core):
+        assert not core.phases_fp32(2)
+        return core.metric_flat_batch(D, torch.zeros_like(D), W, 1.0)
+
+    def jacobian():
+        # a copy of the point: the model hands out its last Jacobian again
+        # for the very same latent tensors
+        return cf(ift.Linearization.make_var(1. * pos)).jac
+    core = jacobian()
+    Q1 = metric(core)
+    W.mul_(2.)
+    Q2 = metric(core)
+    fresh = jacobian()
+    assert fresh is not core
+    Q_ref = metric(fresh)
+    assert torch.equal(Q2, Q_ref)
+    a, b = core.grid_segment()
+    assert not torch.equal(Q1[:, a:b], Q2[:, a:b])
 
 
 @pytest.mark.parametrize("shape,args", CASES + [((4096, 4096), CF_ARGS)])
