@@ -48,6 +48,8 @@
  *   nft_samp_*         MaskOperator.apply, src/operators/mask_operator.py:50-59, and
  *                      LinearInterpolator.apply (scipy COO matvec / rmatvec of
  *                      _build_mat), src/operators/linear_interpolation.py:69-103
+ *   nft_conv_*         FuncConvolutionOperator.apply,
+ *                      src/operators/convolution_operators.py
  *   nft_lh_*           BernoulliEnergy / StudentTEnergy / InverseGammaEnergy value,
  *                      gradient, Fisher weight and Bernoulli's transformation,
  *                      src/operators/energy_operators.py:628-761
@@ -907,6 +909,41 @@ int nft_prod_vjp_batched(int64_t B1, int64_t B2, const double* consts, double s1
                          int64_t g_stride, double* gm1, int64_t gm1_stride, double* gm2, int64_t gm2_stride,
                          double* out_zm, const double* d_zm, int64_t lat_stride, double shift, double* ws, int nrhs,
                          hipStream_t stream);
+
+/* ---- convolution response ---------------------------------------------- */
+/* FuncConvolutionOperator (src/operators/convolution_operators.py): the
+ * periodic convolution C x = Re ifftn(kt * fftn(x)) with a real kernel kt that
+ * is even under k -> -k and has kt[0] = 1.  C is symmetric: the adjoint is
+ * the same call.
+ *   table   device fp64, kt / (number of pixels) on the half grid
+ *           shape[0] x ... x (shape[ndim-1] / 2 + 1), C order. */
+typedef struct nft_conv_plan {
+  int ndim; /* 1..3 */
+  int64_t shape[3];
+  const double* table;
+} nft_conv_plan;
+
+/* 1 where the native pipeline serves the grid: fp64 (dtype 0), 2-D or 3-D,
+ * every axis a power of two -- the last 8..8192, the middle one of a 3-D grid
+ * 8..512, the first 8..512 or 1024..16384 -- and fewer than 2^31 pixels. */
+int nft_conv_supported(int ndim, const int64_t* shape, int dtype);
+/* bytes of workspace for nvec vectors (the half spectra); 0 for a bad plan */
+size_t nft_conv_workspace(const nft_conv_plan* plan, int nvec);
+/* quadratic-form partials per vector; 0 where the grid is not supported */
+int nft_conv_quad_blocks(const nft_conv_plan* plan);
+/* With t = C(colscale * x[v]) (colscale NULL: ones), y[v] = scale * rowscale *
+ * t (rowscale NULL: ones); colscale and rowscale are shared by the batch, x[v]
+ * = x + v * x_stride and y[v] = y + v * y_stride (element strides, at least a
+ * vector long; y may not alias x or ws).  qpart (NULL: none): qpart[v * qstride
+ * + b] = the fp64 sum of t_j * y_j over block b's pixels, b <
+ * nft_conv_quad_blocks(plan), in a fixed order independent of nvec; vector v
+ * of a batched call is bitwise the nvec = 1 call.  No atomics, no allocation,
+ * no synchronisation: capturable.  NFT_ERR_ARG for a bad plan (ndim outside
+ * 1..3, NULL table), NULL vectors, nvec < 1, short strides or workspace;
+ * NFT_ERR_UNSUPPORTED where nft_conv_supported is 0. */
+int nft_conv_apply_batched(const nft_conv_plan* plan, const void* x, int64_t x_stride, const void* colscale,
+                           void* y, int64_t y_stride, const void* rowscale, double scale, int nvec, int dtype,
+                           double* qpart, int64_t qstride, void* ws, size_t ws_bytes, hipStream_t stream);
 
 /* ---- launch profiler (HIP events) -------------------------------------- */
 /* Between nft_prof_begin and nft_prof_end every hot-path kernel launch

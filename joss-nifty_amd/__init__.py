@@ -38,6 +38,7 @@ from .operators.adder import Adder
 from .operators.block_diagonal_operator import BlockDiagonalOperator
 from .operators.chain_operator import ChainOperator
 from .operators.contraction_operator import ContractionOperator, IntegrationOperator
+from .operators.convolution_operators import FuncConvolutionOperator
 from .operators.diagonal_operator import DiagonalOperator
 from .operators.distributors import DOFDistributor, PowerDistributor
 from .operators.endomorphic_operator import EndomorphicOperator

@@ -70,6 +70,10 @@ SIGNATURES = {
     "nft_samp_quad_blocks": (_i, [_p]),
     "nft_samp_forward_batched": (_i, [_p, _p, _p, _i64, _p, _p, _i, _d, _i, _i64, _i64, _p, _i64, _p]),
     "nft_samp_adjoint_batched": (_i, [_p, _p, _p, _p, _i64, _p, _i, _d, _i, _i64, _i64, _p]),
+    "nft_conv_supported": (_i, [_i, _p, _i]),
+    "nft_conv_workspace": (_sz, [_p, _i]),
+    "nft_conv_quad_blocks": (_i, [_p]),
+    "nft_conv_apply_batched": (_i, [_p, _p, _i64, _p, _p, _i64, _p, _d, _i, _i, _p, _i64, _p, _sz, _p]),
     "nft_cg_dd_blocks": (_i, [_i64]),
     "nft_cg_direction_dd_batched": (_i, [_p, _p, _i64, _i64, _i, _i, _p, _d, _p, _i64, _p]),
     "nft_fold_partials": (_i, [_p, _i, _i, _p, _i64, _p]),
@@ -151,6 +155,11 @@ class SampPlan(ctypes.Structure):
     """nft_samp_plan (include/nifty_amd.h)."""
     _fields_ = [("npoints", _i64), ("npix", _i64), ("ndim", _i), ("ncorner", _i), ("shape", _i64 * 3)] + \
                [(n, _p) for n in ("point", "idx", "frac", "pix_ptr", "ent")]
+
+
+class ConvPlan(ctypes.Structure):
+    """nft_conv_plan (include/nifty_amd.h)."""
+    _fields_ = [("ndim", _i), ("shape", _i64 * 3), ("table", _p)]
 
 
 class AmpConst(ctypes.Structure):
@@ -815,6 +824,58 @@ def samp_adjoint(plan, y, out, colscale=None, rowscale=None, scale=1.0):
                                         dtype_code(y.dtype), float(scale), k, y[0].numel(), out[0].numel(),
                                         stream_ptr()))
     return out
+
+
+CONV_KMAX = 8      # vectors per batched convolution call
+
+
+def conv_supported(shape, dtype=torch.float64):
+    """1 where nft_conv_apply_batched serves the grid (nft_conv_supported)."""
+    sh = (ctypes.c_int64 * max(len(shape), 1))(*shape)
+    return bool(load().nft_conv_supported(len(shape), sh, dtype_code(dtype)))
+
+
+def conv_plan(shape, table):
+    """ConvPlan of a grid and its device fp64 table kt / npix on the half grid
+    (the caller keeps the table alive)."""
+    if not (table.is_cuda and table.dtype == torch.float64 and table.is_contiguous()):
+        raise NativeError("conv table: a contiguous fp64 device tensor")
+    p = ConvPlan()
+    p.ndim = len(shape)
+    for i, n in enumerate(shape):
+        p.shape[i] = int(n)
+    p.table = table.data_ptr()
+    return p
+
+
+def conv_quad_blocks(plan):
+    return int(load().nft_conv_quad_blocks(ctypes.byref(plan)))
+
+
+def conv_apply(plan, x, y, colscale=None, rowscale=None, scale=1.0, qpart=None):
+    """y[b] = scale * rowscale * C (colscale * x[b]) (nft_conv_apply_batched):
+    x, y (k, npix) fp64 device rows with unit element stride, any row stride;
+    colscale / rowscale shared grid vectors; qpart (k, >= nft_conv_quad_blocks)
+    fp64 rows or None."""
+    lib = load()
+    require_device(colscale, rowscale)
+    for t in (x, y):
+        if not (t.is_cuda and t.dim() == 2 and t.stride(1) == 1):
+            raise NativeError("conv: (k, npix) device rows with unit element stride; no CPU fallback exists")
+    k = x.shape[0]
+    qs = 0
+    if qpart is not None:
+        if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1
+                and qpart.shape[0] >= k):
+            raise NativeError("qpart: (k, >= nft_conv_quad_blocks) fp64 device rows with unit element stride")
+        qs = qpart.stride(0)
+    nbytes = lib.nft_conv_workspace(ctypes.byref(plan), k)
+    ws = workspace(nbytes, x.device, "conv")
+    _check(lib.nft_conv_apply_batched(ctypes.byref(plan), ptr(x), x.stride(0) if k > 1 else x.shape[1], ptr(colscale),
+                                      ptr(y), y.stride(0) if k > 1 else y.shape[1], ptr(rowscale), float(scale), k,
+                                      dtype_code(x.dtype), ptr(qpart), qs, ptr(ws), ctypes.c_size_t(ws.numel()),
+                                      stream_ptr()))
+    return y
 
 
 def mirror_mix(x, y, shape, split, rows=1, x_stride=0, y_stride=0):

@@ -1332,6 +1332,11 @@ static int c2c_impl(const void* in, void* out, const Geo& g, const std::vector<i
   return NFT_OK;
 }
 
+// one engine-v2 fp64 pass for the other translation units (nft_conv.hip)
+int fast_pass_f64(int kind, bool rows, int N, fast::FastArgs<double>& a, hipStream_t s) {
+  return fast::launch<double>(kind, rows, N, a, s);
+}
+
 }  // namespace nft
 
 using namespace nft;

@@ -202,6 +202,23 @@ class RGSpace(StructuredDomain):
         tol = 1e-12 * tmp[-1]
         return tmp[np.diff(np.r_[tmp, 2 * tmp[-1]]) > tol]
 
+    def get_conv_kernel_from_func(self, func):
+        """Harmonic-space Field of the convolution kernel of the radially
+        symmetric `func` of the distance from the centre, in the units of the
+        position space (rg_space.py:161-181): func on the distance array of
+        the position partner, normalised to unit integral, weighted with the
+        pixel volume and transformed by the adjoint harmonic transform.  The
+        kernel is even, so its Hartley transform is the real part of its FFT.
+        Computed on the host (setup only)."""
+        if not self.harmonic:
+            raise NotImplementedError
+        from ..field import Field
+        pos = self.get_default_codomain()
+        ker = np.asarray(func(pos._dist_array()), dtype=np.float64)
+        ker = ker / (ker.sum() * pos.scalar_dvol)
+        ker = ker * pos.scalar_dvol
+        return Field.from_raw(self, np.fft.fftn(ker).real * self.scalar_dvol)
+
     def get_default_codomain(self):
         return RGSpace(self.shape, None, not self.harmonic, self._rdistances)
 

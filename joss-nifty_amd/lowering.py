@@ -14,7 +14,8 @@ per expansion point into a composition of native calls on raw device tensors:
   * the correlated-field Jacobian (CFJacobian) runs its fused transforms,
   * runs of pointwise factors around a LOSResponse are folded into the LOS
     kernels' column / row scales (nft_los_*); likewise around a MaskOperator
-    or LinearInterpolator (nft_samp_*),
+    or LinearInterpolator (nft_samp_*) and a FuncConvolutionOperator
+    (nft_conv_*),
   * a sum "alpha * 1 + X" whose X ends in a CF Jacobian adjoint is folded
     into that adjoint's epilogue (out = alpha * x + X x).
 
@@ -73,6 +74,7 @@ def _adj_parts(op, adjoint):
 def _lower_leaf(op, adjoint):
     from .library.correlated_fields_simple import CFJacobian
     from .library.los_response import LOSResponse
+    from .operators.convolution_operators import FuncConvolutionOperator
     from .operators.sampling_plan import SamplingResponse
     op, adjoint = _adj_parts(op, adjoint)
     if _is_real_scale(op) and isinstance(op.domain, MultiDomain):
@@ -107,6 +109,8 @@ def _lower_leaf(op, adjoint):
         return _los(op, adjoint, None, None, 1.0)
     if isinstance(op, SamplingResponse):
         return _samp(op, adjoint, None, None, 1.0)
+    if isinstance(op, FuncConvolutionOperator):
+        return _conv(op, adjoint, None, None, 1.0)
     raise _Unsupported(op)
 
 
@@ -150,6 +154,20 @@ def _samp(R, adjoint, cin, cout, scale):
     return f
 
 
+def _conv(C, adjoint, cin, cout, scale):
+    """A FuncConvolutionOperator (symmetric: its adjoint is the same map) with
+    the pointwise factors cin / cout and `scale` folded into the one
+    nft_conv_apply_batched call, as _samp."""
+    gshape = C.domain.shape
+    cin = None if cin is None else cin.reshape(-1).contiguous()
+    cout = None if cout is None else cout.reshape(-1).contiguous()
+
+    def f(x, acc=None, alpha=0.):
+        y = C.apply_rows(x.reshape(1, -1).contiguous(), colscale=cin, rowscale=cout, scale=scale)
+        return _finish(y.reshape(gshape), acc, alpha)
+    return f
+
+
 def _fold(items):
     """product of pointwise items -> (tensor or None, float scale)"""
     t, s = None, 1.0
@@ -164,6 +182,7 @@ def _fold(items):
 def _lower_chain(ops, adjoint):
     """ops: chain factors outermost first.  Returns a callable."""
     from .library.los_response import LOSResponse
+    from .operators.convolution_operators import FuncConvolutionOperator
     from .operators.sampling_plan import SamplingResponse
     seq = [(_adj_parts(op, adjoint)) for op in (reversed(ops) if adjoint else ops)]
     # application order: innermost first
@@ -172,7 +191,7 @@ def _lower_chain(ops, adjoint):
     i = 0
     while i < len(seq):
         op, adj = seq[i]
-        if isinstance(op, (LOSResponse, SamplingResponse)):
+        if isinstance(op, (LOSResponse, SamplingResponse, FuncConvolutionOperator)):
             # absorb the pointwise run before (input side) and after (output side)
             pre = []
             while fns and fns[-1][0] == "pw":
@@ -184,7 +203,11 @@ def _lower_chain(ops, adjoint):
                 j += 1
             cin, s_in = _fold(pre)
             cout, s_out = _fold(post)
-            lower_r = _los if isinstance(op, LOSResponse) else _samp
+            lower_r = _samp
+            if isinstance(op, LOSResponse):
+                lower_r = _los
+            elif isinstance(op, FuncConvolutionOperator):
+                lower_r = _conv
             fns.append(("fn", lower_r(op, adj, cin, cout, s_in * s_out)))
             i = j
             continue

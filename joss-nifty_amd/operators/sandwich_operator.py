@@ -80,8 +80,12 @@ def _pointwise_diag(ops):
 
 def _fused_response_middle(left, cheese, fct):
     """Middle M^T C M for left = [data-side pointwise..., R, grid-side
-    pointwise...] with R providing `fused_middle` (LOSResponse), else None."""
+    pointwise...] with R providing `fused_middle` (LOSResponse, the sampling
+    responses, FuncConvolutionOperator), or for the one fused chain of two
+    responses (_masked_convolution_middle), else None."""
     ir = [i for i, op in enumerate(left) if hasattr(op, "fused_middle")]
+    if len(ir) == 2:
+        return _masked_convolution_middle(left, ir, cheese, fct)
     if len(ir) != 1:
         return None
     i = ir[0]
@@ -98,6 +102,40 @@ def _fused_response_middle(left, cheese, fct):
     if torch.is_tensor(c) and c.numel() not in (1, R.target.size):
         return None
     return R.fused_middle(dr, c, fct)
+
+
+def _masked_convolution_middle(left, ir, cheese, fct):
+    """The one two-response composition that is fused: left = [data-side
+    pointwise..., MaskOperator, pointwise..., FuncConvolutionOperator,
+    grid-side pointwise...] (the instrument model Mask(Exposure(PSF(.)))).
+    The mask's sandwich with the pointwise run between it and the convolution
+    is a grid tensor, which is the convolution middle's data weight.  Every
+    other two-response mix: None."""
+    from .convolution_operators import FuncConvolutionOperator
+    from .mask_operator import MaskOperator
+    im, ic = ir
+    M, C = left[im], left[ic]
+    if not (isinstance(M, MaskOperator) and isinstance(C, FuncConvolutionOperator)):
+        return None
+    c = _pointwise_weight(left[:im], cheese)
+    between = _pointwise_diag(left[im + 1:ic])
+    dr = _pointwise_diag(left[ic + 1:])
+    if c is None or between is False or dr is False:
+        return None
+    if torch.is_tensor(c) and c.numel() not in (1, M.target.size):
+        return None
+    f2 = 1.0
+    if between is not None and not torch.is_tensor(between):
+        f2 = float(between) ** 2
+        between = None
+    if between is not None and between.numel() != M.domain.size:
+        return None
+    if dr is not None and not torch.is_tensor(dr):
+        fct *= float(dr) ** 2
+        dr = None
+    if dr is not None and dr.numel() != C.domain.size:
+        return None
+    return C.fused_middle(dr, M.fused_middle(between, c, f2), fct)
 
 
 def _chain_fusion(ops, cheese0):
