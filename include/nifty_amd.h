@@ -945,6 +945,49 @@ int nft_conv_apply_batched(const nft_conv_plan* plan, const void* x, int64_t x_s
                            void* y, int64_t y_stride, const void* rowscale, double scale, int nvec, int dtype,
                            double* qpart, int64_t qstride, void* ws, size_t ws_bytes, hipStream_t stream);
 
+/* ---- convolution on one space of a product domain ---------------------- */
+/* FuncConvolutionOperator(domain, func, space=0) on a two-space domain
+ * (S, X), S a 2-D position RGSpace n0 x n1, X the rest with ne pixels:
+ *   C x = Re ifftn_S(k * fftn_S(x)) + (1 - k0) * mean(x)
+ * with k the RAW harmonic-space kernel of S (zero mode k0, not 1), broadcast
+ * over X, and the mean over ALL pixels of both spaces (the reference
+ * subtracts the mean of the whole field).  C is symmetric: the adjoint is the
+ * same call.  A vector is the C-ordered real array (n0, n1, ne), ne even; its
+ * reinterpretation as complex (n0, n1, ne / 2) packs the slices 2j and 2j + 1
+ * as real and imaginary part, and k is real, so full-length complex
+ * transforms over axes 0 and 1 convolve both slices at once.
+ *   table   device fp64, k / (n0 * n1) on the full grid n0 x n1, C order. */
+typedef struct nft_conv_space_plan {
+  int64_t n0, n1, inner; /* inner = ne / 2 complex values per pixel of S */
+  const double* table;   /* raw k / (n0 * n1), full grid n0 x n1, C order */
+  double gain0;          /* k0 */
+} nft_conv_space_plan;
+
+/* 1 where the native pipeline serves the domain: fp64 (dtype 0), n0 and n1
+ * powers of two -- n1 8..512, n0 8..512 or 1024..16384 -- ne even and at
+ * least 2, and fewer than 2^31 pixels. */
+int nft_conv_space_supported(int64_t n0, int64_t n1, int64_t ne, int dtype);
+/* bytes of workspace for nvec vectors (the complex grids, the mean partials
+ * and the mean terms); 0 for a bad plan */
+size_t nft_conv_space_workspace(const nft_conv_space_plan* plan, int nvec);
+/* quadratic-form partials per vector; 0 where the domain is not supported */
+int nft_conv_space_quad_blocks(const nft_conv_space_plan* plan);
+/* With t = C(colscale * x[v]) (colscale NULL: ones), y[v] = scale * rowscale *
+ * t (rowscale NULL: ones); colscale and rowscale are shared by the batch, x[v]
+ * = x + v * x_stride and y[v] = y + v * y_stride (element strides, at least a
+ * vector long; y may not alias x or ws).  The mean is that of colscale * x[v].
+ * qpart (NULL: none): qpart[v * qstride + b] = the fp64 sum of t_j * y_j over
+ * block b's pixels, b < nft_conv_space_quad_blocks(plan), in a fixed order
+ * independent of nvec; the mean is folded in an order fixed by the plan;
+ * vector v of a batched call is bitwise the nvec = 1 call.  No atomics, no
+ * allocation, no synchronisation: capturable.  NFT_ERR_ARG for a bad plan
+ * (n0, n1 or inner < 1, NULL table), NULL vectors, nvec < 1, short strides or
+ * workspace; NFT_ERR_UNSUPPORTED where nft_conv_space_supported is 0. */
+int nft_conv_space_apply_batched(const nft_conv_space_plan* plan, const void* x, int64_t x_stride,
+                                 const void* colscale, void* y, int64_t y_stride, const void* rowscale, double scale,
+                                 int nvec, int dtype, double* qpart, int64_t qstride, void* ws, size_t ws_bytes,
+                                 hipStream_t stream);
+
 /* ---- launch profiler (HIP events) -------------------------------------- */
 /* Between nft_prof_begin and nft_prof_end every hot-path kernel launch
  * records a HIP event on its stream just before the launch; nft_prof_end

@@ -74,6 +74,10 @@ SIGNATURES = {
     "nft_conv_workspace": (_sz, [_p, _i]),
     "nft_conv_quad_blocks": (_i, [_p]),
     "nft_conv_apply_batched": (_i, [_p, _p, _i64, _p, _p, _i64, _p, _d, _i, _i, _p, _i64, _p, _sz, _p]),
+    "nft_conv_space_supported": (_i, [_i64, _i64, _i64, _i]),
+    "nft_conv_space_workspace": (_sz, [_p, _i]),
+    "nft_conv_space_quad_blocks": (_i, [_p]),
+    "nft_conv_space_apply_batched": (_i, [_p, _p, _i64, _p, _p, _i64, _p, _d, _i, _i, _p, _i64, _p, _sz, _p]),
     "nft_cg_dd_blocks": (_i, [_i64]),
     "nft_cg_direction_dd_batched": (_i, [_p, _p, _i64, _i64, _i, _i, _p, _d, _p, _i64, _p]),
     "nft_fold_partials": (_i, [_p, _i, _i, _p, _i64, _p]),
@@ -160,6 +164,11 @@ class SampPlan(ctypes.Structure):
 class ConvPlan(ctypes.Structure):
     """nft_conv_plan (include/nifty_amd.h)."""
     _fields_ = [("ndim", _i), ("shape", _i64 * 3), ("table", _p)]
+
+
+class ConvSpacePlan(ctypes.Structure):
+    """nft_conv_space_plan (include/nifty_amd.h)."""
+    _fields_ = [("n0", _i64), ("n1", _i64), ("inner", _i64), ("table", _p), ("gain0", _d)]
 
 
 class AmpConst(ctypes.Structure):
@@ -875,6 +884,57 @@ def conv_apply(plan, x, y, colscale=None, rowscale=None, scale=1.0, qpart=None):
                                       ptr(y), y.stride(0) if k > 1 else y.shape[1], ptr(rowscale), float(scale), k,
                                       dtype_code(x.dtype), ptr(qpart), qs, ptr(ws), ctypes.c_size_t(ws.numel()),
                                       stream_ptr()))
+    return y
+
+
+def conv_space_supported(n0, n1, ne, dtype=torch.float64):
+    """1 where nft_conv_space_apply_batched serves the convolution over the
+    n0 x n1 space 0 of an (n0, n1, ne) domain (nft_conv_space_supported)."""
+    return bool(load().nft_conv_space_supported(int(n0), int(n1), int(ne), dtype_code(dtype)))
+
+
+def conv_space_plan(n0, n1, ne, table, gain0):
+    """ConvSpacePlan of an (n0, n1, ne) domain, ne even, and its device fp64
+    table k / (n0 * n1) on the full n0 x n1 grid (the caller keeps the table
+    alive); gain0 the kernel's zero mode k0."""
+    if not (table.is_cuda and table.dtype == torch.float64 and table.is_contiguous()
+            and table.numel() == int(n0) * int(n1)):
+        raise NativeError("conv space table: a contiguous fp64 device tensor of n0 * n1 values")
+    if int(ne) < 2 or int(ne) % 2:
+        raise NativeError("conv space plan: an even number of pixels in the second space")
+    p = ConvSpacePlan()
+    p.n0, p.n1, p.inner = int(n0), int(n1), int(ne) // 2
+    p.table = table.data_ptr()
+    p.gain0 = float(gain0)
+    return p
+
+
+def conv_space_quad_blocks(plan):
+    return int(load().nft_conv_space_quad_blocks(ctypes.byref(plan)))
+
+
+def conv_space_apply(plan, x, y, colscale=None, rowscale=None, scale=1.0, qpart=None):
+    """y[b] = scale * rowscale * C (colscale * x[b]) (nft_conv_space_apply_batched),
+    C the convolution over space 0 with the global-mean term: the arguments
+    of conv_apply, qpart (k, >= nft_conv_space_quad_blocks)."""
+    lib = load()
+    require_device(colscale, rowscale)
+    for t in (x, y):
+        if not (t.is_cuda and t.dim() == 2 and t.stride(1) == 1):
+            raise NativeError("conv: (k, npix) device rows with unit element stride; no CPU fallback exists")
+    k = x.shape[0]
+    qs = 0
+    if qpart is not None:
+        if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1
+                and qpart.shape[0] >= k):
+            raise NativeError("qpart: (k, >= nft_conv_space_quad_blocks) fp64 device rows with unit element stride")
+        qs = qpart.stride(0)
+    nbytes = lib.nft_conv_space_workspace(ctypes.byref(plan), k)
+    ws = workspace(nbytes, x.device, "conv_space")
+    _check(lib.nft_conv_space_apply_batched(ctypes.byref(plan), ptr(x), x.stride(0) if k > 1 else x.shape[1],
+                                            ptr(colscale), ptr(y), y.stride(0) if k > 1 else y.shape[1],
+                                            ptr(rowscale), float(scale), k, dtype_code(x.dtype), ptr(qpart), qs,
+                                            ptr(ws), ctypes.c_size_t(ws.numel()), stream_ptr()))
     return y
 
 

@@ -22,6 +22,11 @@
 // allocation: capturable in a HIP graph.  Every line is transformed by the
 // same arithmetic whatever tile it lands in, and the C2R tiles never straddle
 // two vectors, so vector v of a batched call is bitwise the single call.
+//
+// nft_conv_space_*: the same operator on space 0 of a two-space domain, three
+// passes over the data with the global-mean term of the reference's product
+// domain form (see "sub-space passes" below).
+#include <cstdint>
 #include <cstring>
 
 #include "fast_dispatch.hpp"
@@ -43,6 +48,11 @@ struct SandArgs {
   const C* tw2;         // four-step twiddle table of length Nfull (or null)
   const double* table;  // kt / Npix, [n_axis][I]
   int km, kx, Nfull;    // full-axis index k = m * km + x * kx
+  // table index mode: inner == 0: [k][column]; inner >= 1 (sub-space
+  // convolution): [k][column / inner], tcols = I / inner table columns, the
+  // table broadcast over the `inner` adjacent columns of one pixel
+  int inner;
+  long long tcols;
 };
 
 template <int N, int NT, int VP>
@@ -80,7 +90,8 @@ __global__ __launch_bounds__(NT) void sandwich_kernel(SandArgs a) {
     const int x = e >> SHL, l = e & (L - 1);
     const long long li = tl.i0 + l;
     const long long k = (long long)m * a.km + (long long)x * a.kx;
-    const double w = li < g.I ? a.table[k * g.I + li] : 0.0;
+    double w = 0.0;
+    if (li < g.I) w = a.inner ? a.table[k * a.tcols + (unsigned)li / (unsigned)a.inner] : a.table[k * g.I + li];
     const C v = lds[l * PITCH + padx<PS>(x)];
     lds[l * PITCH + padx<PS>(x)] = C{v.x * w, -(v.y * w)};
   }
@@ -284,6 +295,219 @@ static int launch_r2c(int N, FastArgs<double>& a, hipStream_t s) { return fast_p
 
 static int launch_c2c_strided(int N, FastArgs<double>& a, hipStream_t s) {
   return fast_pass_f64(K_C2C, false, N, a, s);
+}
+
+// ------------------------------------------------------------ sub-space passes
+// Convolution over space 0 of a two-space domain (S = n0 x n1, X = ne pixels,
+// ne even): the real array (n0, n1, ne) is read as complex (n0, n1, inner),
+// inner = ne / 2, so slices 2j and 2j + 1 of X travel as real and imaginary
+// part through full-length C2C transforms over axes 1 and 0 and a REAL table.
+//   1. axis-1 forward pass: colscale and the vector stride in the prologue,
+//      per-tile sums of the k1 = 0 outputs (the line sums) for the mean
+//   2. mean fold: cmean[v] = (1 - k0) * mean(colscale * x[v])
+//   3. the column sandwich over axis 0, table indexed [k0][k1]
+//   4. axis-1 inverse pass: t = value + cmean[v], y = scale * rowscale * t,
+//      per-tile partials of t . y
+// A line of the axis-1 passes is (r0, i): elements (r0, x, i), x < n1, at
+// complex offset (r0 * n1 + x) * inner + i.  The lines of one vector are
+// numbered q = r0 * inner + i and tiled L at a time over q, so a tile spans
+// several r0 where inner < L (no idle lanes) and never two vectors.
+struct SpaceArgs {
+  const double* x;  // forward: input vectors
+  long long xs;
+  const double* colscale;
+  C* buf;  // [nvec][n0][n1][inner]
+  const C* tw;
+  double* y;  // inverse: output vectors
+  long long ys;
+  const double* rowscale;
+  double scale;
+  const double* cmean;  // inverse: [nvec]
+  double* part;         // forward: mean partials; inverse: qpart (or null)
+  long long pstride;
+  long long lines;  // n0 * inner lines per vector
+  int inner, tpv;   // tiles per vector
+  int al;           // x / colscale (y / rowscale) allow 16-byte accesses
+};
+
+constexpr int SP_NT = 256;
+constexpr int sp_lines(int N) { return SP_NT * VPT / N; }
+static size_t sp_lds_align(size_t b) { return (b + 15) & ~(size_t)15; }
+
+__device__ __forceinline__ C ld2(const double* p, int al) {
+  if (al) return *(const C*)p;
+  return C{p[0], p[1]};
+}
+
+// fixed-order block sum: wave shuffle trees, then the waves in order (as
+// c2r_kernel); the result is valid in thread 0.  sh: NT / 64 doubles of LDS
+// free for use (synced here before it is written)
+template <int NT>
+__device__ __forceinline__ double block_sum(double s, double* sh, int tid) {
+  __syncthreads();
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((tid & 63) == 0) sh[tid >> 6] = s;
+  __syncthreads();
+  double r = 0.0;
+  if (tid == 0)
+    for (int w = 0; w < NT / 64; ++w) r += sh[w];
+  return r;
+}
+
+template <int N, bool INV>
+__global__ __launch_bounds__(SP_NT) void space_axis1_kernel(SpaceArgs a) {
+  constexpr int NT = SP_NT;
+  constexpr int L = sp_lines(N);
+  static_assert(L >= 1 && NT % L == 0, "a thread keeps one line through the load and store loops");
+  constexpr int PITCH = pass_pitch<N, false>();
+  constexpr int PS = pass_pad<N, false>();
+  constexpr int SHL = ilog2(L);
+  constexpr int XS = NT / L;  // x step between a thread's values
+  extern __shared__ __align__(16) unsigned char smem[];
+  C* lds = (C*)smem;
+  C* twq = (C*)(smem + (((size_t)L * PITCH * sizeof(C) + 15) & ~(size_t)15));
+  const int tid = threadIdx.x;
+  for (int r = tid; r < N / 4; r += NT) twq[r] = a.tw[r];  // synced before the first stage
+  const long long item = (long long)blockIdx.x / a.tpv;
+  const int tt = (int)((long long)blockIdx.x - item * a.tpv);
+  const int l = tid & (L - 1);
+  const int x0 = tid >> SHL;
+  const long long q = (long long)tt * L + l;
+  const bool live = q < a.lines;
+  const unsigned r0 = live ? (unsigned)q / (unsigned)a.inner : 0u;
+  const unsigned i = live ? (unsigned)q - r0 * (unsigned)a.inner : 0u;
+  const long long off0 = (long long)r0 * N * a.inner + i;  // complex offset of element x = 0
+  const long long P2 = a.lines * N;                        // complex values per vector
+  C* buf = a.buf + item * P2;
+#pragma unroll
+  for (int r = 0; r < VPT; ++r) {
+    const int x = x0 + r * XS;
+    const long long off = off0 + (long long)x * a.inner;
+    C v = C{0.0, 0.0};
+    if (live) {
+      if constexpr (INV) {
+        v = buf[off];
+        v.y = -v.y;
+      } else {
+        v = ld2(a.x + item * a.xs + 2 * off, a.al);
+        if (a.colscale) {
+          const C c = ld2(a.colscale + 2 * off, a.al);
+          v.x *= c.x;
+          v.y *= c.y;
+        }
+      }
+    }
+    lds[l * PITCH + padx<PS>(x)] = v;
+  }
+  __syncthreads();
+  fft<double, N, NT, L, PITCH, PS>(lds, twq, tid);
+  double s = 0.0;
+  if constexpr (!INV) {
+#pragma unroll
+    for (int r = 0; r < VPT; ++r) {
+      const int x = x0 + r * XS;
+      const C w = lds[l * PITCH + padx<PS>(x)];
+      if (live) {
+        buf[off0 + (long long)x * a.inner] = w;
+        if (x == 0) s = w.x + w.y;  // the line's sum, both slices
+      }
+    }
+    const double tot = block_sum<NT>(s, (double*)smem, tid);
+    if (tid == 0) a.part[item * a.pstride + tt] = tot;
+  } else {
+    const double cm = a.cmean[item];
+    double* y = a.y + item * a.ys;
+#pragma unroll
+    for (int r = 0; r < VPT; ++r) {
+      const int x = x0 + r * XS;
+      const C w = lds[l * PITCH + padx<PS>(x)];
+      if (!live) continue;
+      const long long off = off0 + (long long)x * a.inner;
+      const double t0 = w.x + cm, t1 = -w.y + cm;
+      double s0 = a.scale, s1 = a.scale;
+      if (a.rowscale) {
+        const C c = ld2(a.rowscale + 2 * off, a.al);
+        s0 *= c.x;
+        s1 *= c.y;
+      }
+      const double y0 = s0 * t0, y1 = s1 * t1;
+      if (a.al) {
+        *(C*)(y + 2 * off) = C{y0, y1};
+      } else {
+        y[2 * off] = y0;
+        y[2 * off + 1] = y1;
+      }
+      s += t0 * y0;
+      s += t1 * y1;
+    }
+    if (a.part) {
+      const double tot = block_sum<NT>(s, (double*)smem, tid);
+      if (tid == 0) a.part[item * a.pstride + tt] = tot;
+    }
+  }
+}
+
+// cmean[v] = coef * (the sum of vector v's tpv partials): thread t sums the
+// partials t, t + NT, ... in index order, then the fixed-order block sum --
+// an order set by tpv (the plan) alone
+__global__ __launch_bounds__(SP_NT) void space_mean_kernel(const double* part, long long pstride, int tpv, double coef,
+                                                           double* cmean) {
+  __shared__ double sh[SP_NT / 64];
+  const int tid = threadIdx.x;
+  const double* p = part + (long long)blockIdx.x * pstride;
+  double s = 0.0;
+  for (int j = tid; j < tpv; j += SP_NT) s += p[j];
+  const double tot = block_sum<SP_NT>(s, sh, tid);
+  if (tid == 0) cmean[blockIdx.x] = coef * tot;
+}
+
+template <int N, bool INV>
+static int launch_space_axis1_n(const SpaceArgs& a, int nvec, hipStream_t s) {
+  constexpr int L = sp_lines(N);
+  const size_t lds = sp_lds_align((size_t)L * pass_pitch<N, false>() * sizeof(C)) + (size_t)(N / 4) * sizeof(C);
+  static_assert((size_t)L * pass_pitch<N, false>() * sizeof(C) + (N / 4) * sizeof(C) + 16 <= 65536, "LDS");
+  const long long ntiles = (long long)nvec * a.tpv;
+  if (ntiles <= 0) return NFT_OK;
+  if (ntiles > 0x7fffffffLL) {
+    set_last_error("conv: too many tiles");
+    return NFT_ERR_UNSUPPORTED;
+  }
+  prof_mark(s, INV ? (a.part ? "conv_space_inv+quad" : "conv_space_inv") : "conv_space_fwd");
+  hipLaunchKernelGGL((space_axis1_kernel<N, INV>), dim3((unsigned)ntiles), dim3(SP_NT), lds, s, a);
+  NFT_HIP_CHECK(hipGetLastError());
+  return NFT_OK;
+}
+
+template <bool INV>
+static int launch_space_axis1(int N, SpaceArgs& a, int nvec, hipStream_t s) {
+  const void* tw = nullptr;
+  int st = get_twiddles(N, 0, &tw);
+  if (st != NFT_OK) return st;
+  a.tw = (const C*)tw;
+#define NFT_CASE(n) \
+  case n: return launch_space_axis1_n<n, INV>(a, nvec, s);
+  switch (N) { NFT_CASE(8) NFT_CASE(16) NFT_CASE(32) NFT_CASE(64) NFT_CASE(128) NFT_CASE(256) NFT_CASE(512) }
+#undef NFT_CASE
+  set_last_error("conv space: unsupported axis-1 length %d", N);
+  return NFT_ERR_UNSUPPORTED;
+}
+
+static bool space_plan_ok(const nft_conv_space_plan* p) {
+  return p && p->n0 >= 1 && p->n1 >= 1 && p->inner >= 1 && p->table;
+}
+
+static bool space_ok(int64_t n0, int64_t n1, int64_t ne, int dtype) {
+  if (dtype != 0 || n0 < 1 || n1 < 1 || ne < 2 || (ne & 1)) return false;
+  if (n0 > 16384 || n1 > 512 || ne >= 0x7fffffffLL) return false;
+  if ((long long)n0 * n1 * ne >= 0x7fffffffLL) return false;
+  if (!strided_supported((int)n1)) return false;
+  return strided_supported((int)n0) || fourstep_supported((int)n0);
+}
+
+static int space_tiles(const nft_conv_space_plan* p) {
+  const long long L = sp_lines((int)p->n1);
+  return (int)((p->n0 * p->inner + L - 1) / L);
 }
 
 // ------------------------------------------------------------ plan checks
@@ -490,6 +714,164 @@ int nft_conv_apply_batched(const nft_conv_plan* plan, const void* x, int64_t x_s
     a.qpart = qpart;
     a.qstride = qstride;
     if ((st = launch_c2r(N, a, nvec, stream)) != NFT_OK) return st;
+  }
+  return NFT_OK;
+}
+
+// ------------------------------------------------------------ sub-space API
+int nft_conv_space_supported(int64_t n0, int64_t n1, int64_t ne, int dtype) {
+  return space_ok(n0, n1, ne, dtype) ? 1 : 0;
+}
+
+// workspace: the complex grids, then the mean partials, then the mean terms
+static size_t space_ws_grid(const nft_conv_space_plan* p, int nvec) {
+  return align256((size_t)nvec * (size_t)p->n0 * (size_t)p->n1 * (size_t)p->inner * sizeof(C));
+}
+
+size_t nft_conv_space_workspace(const nft_conv_space_plan* plan, int nvec) {
+  if (!space_plan_ok(plan) || nvec < 1) return 0;
+  if (plan->n1 > 512 || plan->n0 > 16384 || plan->inner >= 0x40000000LL) return 0;
+  const size_t tpv = (size_t)space_tiles(plan);
+  return space_ws_grid(plan, nvec) + align256((size_t)nvec * tpv * sizeof(double)) +
+         align256((size_t)nvec * sizeof(double));
+}
+
+int nft_conv_space_quad_blocks(const nft_conv_space_plan* plan) {
+  if (!space_plan_ok(plan) || !space_ok(plan->n0, plan->n1, 2 * plan->inner, 0)) return 0;
+  return space_tiles(plan);
+}
+
+int nft_conv_space_apply_batched(const nft_conv_space_plan* plan, const void* x, int64_t x_stride,
+                                 const void* colscale, void* y, int64_t y_stride, const void* rowscale, double scale,
+                                 int nvec, int dtype, double* qpart, int64_t qstride, void* ws, size_t ws_bytes,
+                                 hipStream_t stream) {
+  if (!space_plan_ok(plan)) {
+    set_last_error("conv space: bad plan (positive n0, n1, inner, table)");
+    return NFT_ERR_ARG;
+  }
+  if (!x || !y || nvec < 1) {
+    set_last_error("conv space: NULL vector or nvec < 1");
+    return NFT_ERR_ARG;
+  }
+  if (plan->inner >= 0x40000000LL || !space_ok(plan->n0, plan->n1, 2 * plan->inner, dtype)) {
+    set_last_error("conv space: domain or dtype not served by the native pipeline (nft_conv_space_supported)");
+    return NFT_ERR_UNSUPPORTED;
+  }
+  const int n0 = (int)plan->n0, n1 = (int)plan->n1, inner = (int)plan->inner;
+  const long long P = (long long)n0 * n1 * inner * 2;  // real pixels per vector
+  if (x_stride < P || y_stride < P) {
+    set_last_error("conv space: vector strides shorter than a vector");
+    return NFT_ERR_ARG;
+  }
+  const int tpv = space_tiles(plan);
+  if (qpart && qstride < tpv) {
+    set_last_error("conv space: qstride shorter than nft_conv_space_quad_blocks");
+    return NFT_ERR_ARG;
+  }
+  const size_t need = nft_conv_space_workspace(plan, nvec);
+  if (!ws || ws_bytes < need) {
+    set_last_error("conv space workspace too small (%zu < %zu)", ws_bytes, need);
+    return NFT_ERR_ARG;
+  }
+  C* grid = (C*)ws;
+  double* mpart = (double*)((char*)ws + space_ws_grid(plan, nvec));
+  double* cmean = (double*)((char*)mpart + align256((size_t)nvec * (size_t)tpv * sizeof(double)));
+  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  int st;
+  SpaceArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.buf = grid;
+  sa.lines = (long long)n0 * inner;
+  sa.inner = inner;
+  sa.tpv = tpv;
+  {  // 1. axis-1 forward pass, colscale and the vector stride in the prologue
+    SpaceArgs a = sa;
+    a.x = (const double*)x;
+    a.xs = x_stride;
+    a.colscale = (const double*)colscale;
+    a.part = mpart;
+    a.pstride = tpv;
+    a.al = al16(x) && (x_stride & 1) == 0 && al16(colscale);
+    if ((st = launch_space_axis1<false>(n1, a, nvec, stream)) != NFT_OK) return st;
+  }
+  // 2. the mean term of every vector
+  prof_mark(stream, "conv_space_mean");
+  hipLaunchKernelGGL(space_mean_kernel, dim3((unsigned)nvec), dim3(SP_NT), 0, stream, (const double*)mpart,
+                     (long long)tpv, tpv, (1.0 - plan->gain0) / (double)P, cmean);
+  NFT_HIP_CHECK(hipGetLastError());
+  const long long I0 = (long long)n1 * inner;  // columns of axis 0
+  if (strided_supported(n0)) {                 // 3. the whole column in one sandwich
+    SandArgs a;
+    memset(&a, 0, sizeof(a));
+    a.buf = grid;
+    a.g.O = nvec;
+    a.g.M = 1;
+    a.g.I = I0;
+    a.g.in_so = I0 * n0;
+    a.g.in_si = 1;
+    a.g.in_sn = I0;
+    a.table = plan->table;
+    a.km = 0;
+    a.kx = 1;
+    a.Nfull = n0;
+    a.inner = inner;
+    a.tcols = n1;
+    if ((st = launch_sandwich(n0, a, stream)) != NFT_OK) return st;
+  } else {
+    int N1, N2;
+    fourstep_split(n0, N1, N2);
+    const void* twN = nullptr;
+    if ((st = get_twiddles(n0, 0, &twN)) != NFT_OK) return st;
+    auto pass_a = [&](int inverse) -> int {  // N1-point FFTs over rows n2 + N2 * j, in place
+      FastArgs<double> a;
+      memset(&a, 0, sizeof(a));
+      a.in = ws;
+      a.out = ws;
+      a.g.O = nvec;
+      a.g.M = N2;
+      a.g.I = I0;
+      a.g.in_so = a.g.out_so = I0 * n0;
+      a.g.in_sm = a.g.out_sm = I0;
+      a.g.in_si = a.g.out_si = 1;
+      a.g.in_sn = a.g.out_sn = I0 * N2;
+      a.tw2 = inverse ? nullptr : twN;  // the sandwich applies the conjugate twiddle
+      a.Nfull = n0;
+      a.conj_in = a.conj_out = inverse;
+      a.scale = 1.0;
+      return launch_c2c_strided(N1, a, stream);
+    };
+    if ((st = pass_a(0)) != NFT_OK) return st;
+    SandArgs a;  // pass B and its inverse: rows N2 * k1 + n2, element k2 is k = k1 + N1 * k2
+    memset(&a, 0, sizeof(a));
+    a.buf = grid;
+    a.g.O = nvec;
+    a.g.M = N1;
+    a.g.I = I0;
+    a.g.in_so = I0 * n0;
+    a.g.in_sm = I0 * N2;
+    a.g.in_si = 1;
+    a.g.in_sn = I0;
+    a.table = plan->table;
+    a.tw2 = (const C*)twN;
+    a.km = 1;
+    a.kx = N1;
+    a.Nfull = n0;
+    a.inner = inner;
+    a.tcols = n1;
+    if ((st = launch_sandwich(N2, a, stream)) != NFT_OK) return st;
+    if ((st = pass_a(1)) != NFT_OK) return st;
+  }
+  {  // 4. axis-1 inverse pass with the epilogue
+    SpaceArgs a = sa;
+    a.y = (double*)y;
+    a.ys = y_stride;
+    a.rowscale = (const double*)rowscale;
+    a.scale = scale;
+    a.cmean = cmean;
+    a.part = qpart;
+    a.pstride = qstride;
+    a.al = al16(y) && (y_stride & 1) == 0 && al16(rowscale);
+    if ((st = launch_space_axis1<true>(n1, a, nvec, stream)) != NFT_OK) return st;
   }
   return NFT_OK;
 }
