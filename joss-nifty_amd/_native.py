@@ -677,18 +677,29 @@ def los_forward_batched(plan, x, y, colscale=None, rowscale=None, scale=1.0):
     return y
 
 
+def _qpart_stride(qpart, k, blocks, ncol=0):
+    """Row stride of the optional curvature partials qpart ((k, >= ncol) fp64
+    device rows with unit element stride; `blocks` names ncol's C function in
+    the error), 0 for None."""
+    if qpart is None:
+        return 0
+    if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1 and qpart.shape[0] >= k
+            and qpart.shape[1] >= ncol):
+        raise NativeError(f"qpart: (k, >= {blocks}) fp64 device rows with unit element stride")
+    return qpart.stride(0)
+
+
 def los_forward_quad_batched(plan, x, y, qpart, colscale=None, rowscale=None, scale=1.0):
     """los_forward_batched plus the per-block partials of sum_l t_l y_l
     (qpart: (k, >= nft_los_quad_blocks) fp64 rows, see nifty_amd.h)."""
     lib = load()
     require_device(x, y, colscale, rowscale)
-    if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1 and qpart.shape[0] >= x.shape[0]):
-        raise NativeError("qpart: (k, >= nft_los_quad_blocks) fp64 device rows with unit element stride")
     k = x.shape[0]
+    qs = _qpart_stride(qpart, k, "nft_los_quad_blocks")
     ws = workspace(k * lib.nft_los_workspace(ctypes.byref(plan)), x.device, "los")
     _check(lib.nft_los_forward_quad_batched(ctypes.byref(plan), ptr(x), ptr(colscale), ptr(rowscale), ptr(y),
                                             ptr(ws), dtype_code(x.dtype), float(scale), k, x[0].numel(),
-                                            y[0].numel(), ptr(qpart), qpart.stride(0), stream_ptr()))
+                                            y[0].numel(), ptr(qpart), qs, stream_ptr()))
     return y
 
 
@@ -737,12 +748,7 @@ def los_forward_ex(plan, x, y, colscale=None, rowscale=None, scale=1.0, qpart=No
     if not (x.is_contiguous() and y.is_contiguous()):
         raise NativeError("los_forward_ex: contiguous x and y required")
     css = _pixel_scale_stride(colscale, k, x[0].numel())
-    qs = 0
-    if qpart is not None:
-        if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1
-                and qpart.shape[0] >= k):
-            raise NativeError("qpart: (k, >= nft_los_quad_blocks) fp64 device rows with unit element stride")
-        qs = qpart.stride(0)
+    qs = _qpart_stride(qpart, k, "nft_los_quad_blocks")
     ws = workspace(k * lib.nft_los_workspace(ctypes.byref(plan)), x.device, "los")
     _check(lib.nft_los_forward_ex(ctypes.byref(plan), ptr(x), ptr(colscale), css, ptr(rowscale), ptr(y), ptr(ws),
                                   dtype_code(x.dtype), float(scale), k, x[0].numel(), y[0].numel(), ptr(qpart), qs,
@@ -781,12 +787,8 @@ def los_adjoint_add(plan, y, out, addw, addx, colscale=None, rowscale=None, scal
         raise NativeError(f"los_adjoint_add: addx holds {addx.numel()} elements for {k} vectors of {npix} pixels")
     rss = _pixel_scale_stride(rowscale, k, npix)
     aws = _pixel_scale_stride(addw, k, npix)
-    qs = 0
-    if qpart is not None:
-        if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1
-                and qpart.shape[0] >= k and qpart.shape[1] >= lib.nft_los_add_blocks(ctypes.byref(plan))):
-            raise NativeError("qpart: (k, >= nft_los_add_blocks) fp64 device rows with unit element stride")
-        qs = qpart.stride(0)
+    qs = 0 if qpart is None else _qpart_stride(qpart, k, "nft_los_add_blocks",
+                                               lib.nft_los_add_blocks(ctypes.byref(plan)))
     _check(lib.nft_los_adjoint_add(ctypes.byref(plan), ptr(y), ptr(colscale), ptr(rowscale), rss, ptr(out),
                                    dtype_code(y.dtype), float(scale), k, y[0].numel(), npix, ptr(addw), aws,
                                    ptr(addx), npix, ptr(qpart), qs, stream_ptr()))
@@ -809,12 +811,7 @@ def samp_forward(plan, x, y, colscale=None, rowscale=None, scale=1.0, qpart=None
     require_device(x, y, colscale, rowscale)
     k = x.shape[0]
     css = _pixel_scale_stride(colscale, k, x[0].numel())
-    qs = 0
-    if qpart is not None:
-        if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1
-                and qpart.shape[0] >= k):
-            raise NativeError("qpart: (k, >= nft_samp_quad_blocks) fp64 device rows with unit element stride")
-        qs = qpart.stride(0)
+    qs = _qpart_stride(qpart, k, "nft_samp_quad_blocks")
     _check(lib.nft_samp_forward_batched(ctypes.byref(plan), ptr(x), ptr(colscale), css, ptr(rowscale), ptr(y),
                                         dtype_code(x.dtype), float(scale), k, x[0].numel(), y[0].numel(),
                                         ptr(qpart), qs, stream_ptr()))
@@ -861,30 +858,32 @@ def conv_quad_blocks(plan):
     return int(load().nft_conv_quad_blocks(ctypes.byref(plan)))
 
 
-def conv_apply(plan, x, y, colscale=None, rowscale=None, scale=1.0, qpart=None):
-    """y[b] = scale * rowscale * C (colscale * x[b]) (nft_conv_apply_batched):
-    x, y (k, npix) fp64 device rows with unit element stride, any row stride;
-    colscale / rowscale shared grid vectors; qpart (k, >= nft_conv_quad_blocks)
-    fp64 rows or None."""
+def _conv_rows(name, plan, x, y, colscale, rowscale, scale, qpart):
+    """the one body of conv_apply (name "conv") and conv_space_apply
+    ("conv_space"): nft_<name>_workspace and nft_<name>_apply_batched take
+    the same arguments after their plan"""
     lib = load()
     require_device(colscale, rowscale)
     for t in (x, y):
         if not (t.is_cuda and t.dim() == 2 and t.stride(1) == 1):
             raise NativeError("conv: (k, npix) device rows with unit element stride; no CPU fallback exists")
     k = x.shape[0]
-    qs = 0
-    if qpart is not None:
-        if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1
-                and qpart.shape[0] >= k):
-            raise NativeError("qpart: (k, >= nft_conv_quad_blocks) fp64 device rows with unit element stride")
-        qs = qpart.stride(0)
-    nbytes = lib.nft_conv_workspace(ctypes.byref(plan), k)
-    ws = workspace(nbytes, x.device, "conv")
-    _check(lib.nft_conv_apply_batched(ctypes.byref(plan), ptr(x), x.stride(0) if k > 1 else x.shape[1], ptr(colscale),
-                                      ptr(y), y.stride(0) if k > 1 else y.shape[1], ptr(rowscale), float(scale), k,
-                                      dtype_code(x.dtype), ptr(qpart), qs, ptr(ws), ctypes.c_size_t(ws.numel()),
-                                      stream_ptr()))
+    qs = _qpart_stride(qpart, k, f"nft_{name}_quad_blocks")
+    nbytes = getattr(lib, f"nft_{name}_workspace")(ctypes.byref(plan), k)
+    ws = workspace(nbytes, x.device, name)
+    _check(getattr(lib, f"nft_{name}_apply_batched")(
+        ctypes.byref(plan), ptr(x), x.stride(0) if k > 1 else x.shape[1], ptr(colscale), ptr(y),
+        y.stride(0) if k > 1 else y.shape[1], ptr(rowscale), float(scale), k, dtype_code(x.dtype), ptr(qpart), qs,
+        ptr(ws), ctypes.c_size_t(ws.numel()), stream_ptr()))
     return y
+
+
+def conv_apply(plan, x, y, colscale=None, rowscale=None, scale=1.0, qpart=None):
+    """y[b] = scale * rowscale * C (colscale * x[b]) (nft_conv_apply_batched):
+    x, y (k, npix) fp64 device rows with unit element stride, any row stride;
+    colscale / rowscale shared grid vectors; qpart (k, >= nft_conv_quad_blocks)
+    fp64 rows or None."""
+    return _conv_rows("conv", plan, x, y, colscale, rowscale, scale, qpart)
 
 
 def conv_space_supported(n0, n1, ne, dtype=torch.float64):
@@ -917,25 +916,7 @@ def conv_space_apply(plan, x, y, colscale=None, rowscale=None, scale=1.0, qpart=
     """y[b] = scale * rowscale * C (colscale * x[b]) (nft_conv_space_apply_batched),
     C the convolution over space 0 with the global-mean term: the arguments
     of conv_apply, qpart (k, >= nft_conv_space_quad_blocks)."""
-    lib = load()
-    require_device(colscale, rowscale)
-    for t in (x, y):
-        if not (t.is_cuda and t.dim() == 2 and t.stride(1) == 1):
-            raise NativeError("conv: (k, npix) device rows with unit element stride; no CPU fallback exists")
-    k = x.shape[0]
-    qs = 0
-    if qpart is not None:
-        if not (qpart.is_cuda and qpart.dtype == torch.float64 and qpart.stride(1) == 1
-                and qpart.shape[0] >= k):
-            raise NativeError("qpart: (k, >= nft_conv_space_quad_blocks) fp64 device rows with unit element stride")
-        qs = qpart.stride(0)
-    nbytes = lib.nft_conv_space_workspace(ctypes.byref(plan), k)
-    ws = workspace(nbytes, x.device, "conv_space")
-    _check(lib.nft_conv_space_apply_batched(ctypes.byref(plan), ptr(x), x.stride(0) if k > 1 else x.shape[1],
-                                            ptr(colscale), ptr(y), y.stride(0) if k > 1 else y.shape[1],
-                                            ptr(rowscale), float(scale), k, dtype_code(x.dtype), ptr(qpart), qs,
-                                            ptr(ws), ctypes.c_size_t(ws.numel()), stream_ptr()))
-    return y
+    return _conv_rows("conv_space", plan, x, y, colscale, rowscale, scale, qpart)
 
 
 def mirror_mix(x, y, shape, split, rows=1, x_stride=0, y_stride=0):

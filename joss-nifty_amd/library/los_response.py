@@ -9,7 +9,6 @@ csrc/nft_los.hip (box_plan): per 256-pixel box, the runs of each line (for
 R x) and the runs of each pixel (for R^T y), float32 weights as in the
 reference, fp64 accumulation in fixed order."""
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -20,6 +19,7 @@ from ..domain_tuple import DomainTuple
 from ..domains import RGSpace, UnstructuredDomain
 from ..field import Field
 from ..operators.linear_operator import LinearOperator
+from ..operators.middle import ResponseMiddle
 
 
 def _gaussian_sf(x):
@@ -137,9 +137,6 @@ def los_coo(shape, distances, starts, ends, sigmas=None, truncation=3.):
 
 LOS_CAP_F = 2048   # entries per forward work item (csrc/nft_los.hip)
 LOS_KMAX = 8       # vectors per batched LOS launch (csrc/nft_los.hip)
-# the carried CG's curvature fold inside the LOS adjoint launch
-# (nft_los_adjoint_fold); NFT_LOS_FOLD=0: its own launch (A/B, tests)
-_FOLD_IN_ADJ = os.environ.get("NFT_LOS_FOLD", "1") != "0"
 BOX = 256
 
 
@@ -315,6 +312,7 @@ class LOSResponse(LinearOperator):
         self._target = DomainTuple.make(UnstructuredDomain(nlos))
         self._plan_np = box_plan(rows, cols, w, sp.shape, nlos)
         self._plan = None
+        self._npix = int(np.prod(sp.shape))
 
     def _box_plan(self):
         """Device copy of the box-blocked layout + its ctypes descriptor."""
@@ -331,94 +329,87 @@ class LOSResponse(LinearOperator):
             self._plan = (d, keep)
         return self._plan[0]
 
+    def _rows(self, sc, k, a, b):
+        """rows a:b of a pixel-side scale: (k, npix) rows, or one vector
+        shared by all k (None, (npix,), (1, npix)) as it is"""
+        if sc is None or sc.numel() == self._npix:
+            return sc
+        return sc.reshape(k, -1)[a:b]
+
+    def _fwd(self, V, colscale=None, rowscale=None, scale=1.0, qpart=None):
+        """rows of V (k, npix) -> scale * rowscale * R (colscale * row), (k,
+        nlos), LOS_KMAX vectors per launch; colscale one pixel vector or (k,
+        npix) rows, applied as the kernel loads the pixels (the same product
+        as a separate multiply); qpart (k, >= nft_los_quad_blocks) fp64 rows:
+        the per-block partials of sum_l t_l y_l, t = R (colscale * row)"""
+        plan = self._box_plan()
+        k = V.shape[0]
+        V = V.contiguous()
+        y = torch.empty((k, self._target.shape[0]), dtype=V.dtype, device=V.device)
+        per = colscale is not None and colscale.numel() != self._npix
+        for a in range(0, k, LOS_KMAX):
+            b = min(k, a + LOS_KMAX)
+            if per:
+                _native.los_forward_ex(plan, V[a:b], y[a:b], colscale=self._rows(colscale, k, a, b),
+                                       rowscale=rowscale, scale=scale, qpart=None if qpart is None else qpart[a:b])
+            elif qpart is not None:
+                _native.los_forward_quad_batched(plan, V[a:b], y[a:b], qpart[a:b], colscale=colscale,
+                                                 rowscale=rowscale, scale=scale)
+            else:
+                _native.los_forward_batched(plan, V[a:b], y[a:b], colscale=colscale, rowscale=rowscale, scale=scale)
+        return y
+
+    def _adj(self, Y, colscale=None, rowscale=None, scale=1.0, fold=None, addw=None, addx=None, qpart=None):
+        """rows of Y (k, nlos) -> scale * rowscale * R^T (colscale * row), (k,
+        npix), LOS_KMAX vectors per launch; rowscale one pixel vector or (k,
+        npix) rows, applied as the pixels are stored.  fold: an
+        nft_fold_partials call (part, nb, nrhs, out address, out stride)
+        carried by the launch that ends at k, the last one
+        (nft_los_adjoint_fold).  addw, addx: + addw * addx[row] as the tile is
+        stored (nft_los_adjoint_add: addw shared or (k, npix) rows, addx (k,
+        npix) rows), with qpart (k, >= nft_los_add_blocks) fp64 rows for the
+        per-box partials of sum addw * addx^2"""
+        plan = self._box_plan()
+        k = Y.shape[0]
+        Y = Y.contiguous()
+        out = torch.empty((k, self._npix), dtype=Y.dtype, device=Y.device)
+        per = rowscale is not None and rowscale.numel() != self._npix
+        if fold is not None and (per or addw is not None):
+            raise NotImplementedError("LOS adjoint: the fold rides in the plain batched launch only")
+        for a in range(0, k, LOS_KMAX):
+            b = min(k, a + LOS_KMAX)
+            rs = self._rows(rowscale, k, a, b)
+            if addw is not None:
+                _native.los_adjoint_add(plan, Y[a:b], out[a:b], self._rows(addw, k, a, b), addx[a:b],
+                                        colscale=colscale, rowscale=rs, scale=scale,
+                                        qpart=None if qpart is None else qpart[a:b])
+            elif per:
+                _native.los_adjoint_ex(plan, Y[a:b], out[a:b], colscale=colscale, rowscale=rs, scale=scale)
+            else:
+                _native.los_adjoint_batched(plan, Y[a:b], out[a:b], colscale=colscale, rowscale=rs, scale=scale,
+                                            fold=fold if b == k else None)
+        return out
+
     def apply(self, x, mode):
         self._check_input(x, mode)
-        v = x.val.reshape(-1).contiguous()
-        plan = self._box_plan()
+        v = x.val.reshape(1, -1)
         if mode == self.TIMES:
-            y = torch.empty(self._target.shape, dtype=v.dtype, device=v.device)
-            _native.los_forward(plan, v, y)
-            return Field(self._target, y)
-        y = torch.empty(self._domain.shape, dtype=v.dtype, device=v.device)
-        _native.los_adjoint(plan, v, y.view(-1))
-        return Field(self._domain, y)
+            return Field(self._target, self._fwd(v).reshape(self._target.shape))
+        return Field(self._domain, self._adj(v).reshape(self._domain.shape))
+
+    def quad_blocks(self):
+        """qpart columns of `_fwd` (nft_los_quad_blocks)"""
+        return int(_native.load().nft_los_quad_blocks(ctypes.byref(self._box_plan())))
 
     def fused_middle(self, dr, c, fct=1.0):
         """Callable s -> fct * dr * R^T (c * R (dr * s)) on grid tensors: the
         middle of a sampling metric J^T D R^T C R D J with pixel-space diagonal
         dr (tensor or None) and data-space weight c (tensor or float) fused
-        into the two SpMV kernels (column / row scales)."""
-        nlos = self._target.shape[0]
-        shape = self._domain.shape
-        drf = None if dr is None else dr.reshape(-1).contiguous()
-        scale = float(fct)
-        cv = None
-        if torch.is_tensor(c):
-            cv = c.reshape(-1).expand(nlos).contiguous()
-        else:
-            scale *= float(c)
-
-        plan = self._box_plan()
-
-        npix = int(np.prod(shape))
-        cast = {}
-
-        def scales(dt):
-            # fp32 CG storage (config.set_cg_precision): scales in the input's dtype
-            if dt == torch.float64:
-                return drf, cv
-            if dt not in cast:
-                cast[dt] = (None if drf is None else drf.to(dt), None if cv is None else cv.to(dt))
-            return cast[dt]
-
-        def middle(s, qpart=None, fold=None):
-            """qpart (optional, (k, >= quad_blocks) fp64): per-block partials of
-            the quadratic form s . middle(s), from the data space.  fold
-            (optional, with qpart): an nft_fold_partials call (part, nb, nrhs,
-            out address, out stride) that needs those partials, carried by
-            the last adjoint launch (nft_los_adjoint_fold)"""
-            drf, cv = scales(s.dtype)
-            if qpart is not None:
-                k = s.shape[0] if s.dim() > len(shape) else 1
-                v = s.reshape(k, npix).contiguous()
-                y = torch.empty((k, nlos), dtype=v.dtype, device=v.device)
-                out = torch.empty((k,) + tuple(shape), dtype=v.dtype, device=v.device)
-                for a in range(0, k, LOS_KMAX):
-                    b = min(k, a + LOS_KMAX)
-                    _native.los_forward_quad_batched(plan, v[a:b], y[a:b], qpart[a:b], colscale=drf, rowscale=cv,
-                                                     scale=scale)
-                    _native.los_adjoint_batched(plan, y[a:b], out[a:b].view(b - a, npix), rowscale=drf,
-                                                fold=fold if b == k else None)
-                return out if s.dim() > len(shape) else out[0]
-            if s.dim() > len(shape):
-                # batch of right-hand sides along a leading axis (batched CG):
-                # the matrix is streamed once per launch for all of them
-                k = s.shape[0]
-                v = s.reshape(k, npix).contiguous()
-                y = torch.empty((k, nlos), dtype=v.dtype, device=v.device)
-                out = torch.empty((k,) + tuple(shape), dtype=v.dtype, device=v.device)
-                for a in range(0, k, LOS_KMAX):
-                    b = min(k, a + LOS_KMAX)
-                    _native.los_forward_batched(plan, v[a:b], y[a:b], colscale=drf, rowscale=cv, scale=scale)
-                    _native.los_adjoint_batched(plan, y[a:b], out[a:b].view(b - a, npix), rowscale=drf)
-                return out
-            v = s.reshape(-1).contiguous()
-            y = torch.empty(nlos, dtype=v.dtype, device=v.device)
-            _native.los_forward(plan, v, y, colscale=drf, rowscale=cv, scale=scale)
-            out = torch.empty(shape, dtype=v.dtype, device=v.device)
-            _native.los_adjoint(plan, y, out.view(-1), rowscale=drf)
-            return out
-        middle.supports_batch = True
-        middle.supports_fp32 = True
-        middle.supports_fold = _FOLD_IN_ADJ
-        middle.quad_blocks = int(_native.load().nft_los_quad_blocks(ctypes.byref(plan)))
-        # what the middle is made of, for a caller that fuses it with further
-        # branches (operators/joint_middle.py); read-only
-        middle.response = self
-        middle.plan = plan
-        middle.scales = scales     # dtype -> (pixel-side diagonal, data-side weight) or None each
-        middle.factor = scale
-        return middle
+        into the two SpMV kernels (column / row scales); the carried CG's
+        curvature fold rides in the last adjoint launch (supports_fold)."""
+        m = ResponseMiddle(self, dr, c, fct, fold=True)
+        m.plan, m.scales = self._box_plan(), m.scales_as
+        return m
 
     @property
     def coo(self):

@@ -24,9 +24,6 @@ y = op(x) + alpha * acc.  The result is the same linear map as the operator
 tree; only the number of passes over HBM and of host round trips changes.
 Unsupported operators make ``lower`` return None (the caller then keeps the
 generic path).  FusedCG captures lowered metrics in a HIP graph."""
-import torch
-
-from . import _native
 from .domain_tuple import DomainTuple
 from .multi_domain import MultiDomain
 
@@ -105,66 +102,25 @@ def _lower_leaf(op, adjoint):
                     op._adjoint_t(x, lay.views(out))
                 return out
         return f
-    if isinstance(op, LOSResponse):
-        return _los(op, adjoint, None, None, 1.0)
-    if isinstance(op, SamplingResponse):
-        return _samp(op, adjoint, None, None, 1.0)
-    if isinstance(op, FuncConvolutionOperator):
-        return _conv(op, adjoint, None, None, 1.0)
+    if isinstance(op, (LOSResponse, SamplingResponse, FuncConvolutionOperator)):
+        return _response(op, adjoint, None, None, 1.0)
     raise _Unsupported(op)
 
 
-def _los(R, adjoint, cin, cout, scale):
-    """R (or R^T) with pointwise input factor cin and output factor cout
-    folded into the kernels (tensors or None) and a scalar `scale`."""
-    plan = R._box_plan()
-    nlos = R.target.shape[0]
-    gshape = R.domain.shape
-    cin = None if cin is None else cin.reshape(-1).contiguous()
-    cout = None if cout is None else cout.reshape(-1).contiguous()
-    if not adjoint:
-        def f(x, acc=None, alpha=0.):
-            y = torch.empty(nlos, dtype=x.dtype, device=x.device)
-            _native.los_forward(plan, x.reshape(-1).contiguous(), y, colscale=cin, rowscale=cout, scale=scale)
-            return _finish(y, acc, alpha)
-    else:
-        def f(x, acc=None, alpha=0.):
-            out = torch.empty(gshape, dtype=x.dtype, device=x.device)
-            _native.los_adjoint(plan, x.reshape(-1).contiguous(), out.view(-1), colscale=cin, rowscale=cout,
-                                scale=scale)
-            return _finish(out, acc, alpha)
-    return f
-
-
-def _samp(R, adjoint, cin, cout, scale):
-    """A sampling response (MaskOperator, LinearInterpolator) or its adjoint
-    with the pointwise factors cin / cout and `scale` folded into the nft_samp
-    launch, as _los; the adjoint writes every pixel (zeros where no datum
-    lands)."""
-    gshape = R.domain.shape
-    cin = None if cin is None else cin.reshape(-1).contiguous()
-    cout = None if cout is None else cout.reshape(-1).contiguous()
-    if not adjoint:
-        def f(x, acc=None, alpha=0.):
-            return _finish(R._fwd(x.reshape(1, -1), colscale=cin, rowscale=cout, scale=scale)[0], acc, alpha)
-    else:
-        def f(x, acc=None, alpha=0.):
-            out = R._adj(x.reshape(1, -1), colscale=cin, rowscale=cout, scale=scale)
-            return _finish(out.reshape(gshape), acc, alpha)
-    return f
-
-
-def _conv(C, adjoint, cin, cout, scale):
-    """A FuncConvolutionOperator (symmetric: its adjoint is the same map) with
-    the pointwise factors cin / cout and `scale` folded into the one
-    nft_conv_apply_batched call, as _samp."""
-    gshape = C.domain.shape
+def _response(R, adjoint, cin, cout, scale):
+    """A response with the row interface of operators/middle.py (LOSResponse,
+    MaskOperator, LinearInterpolator, FuncConvolutionOperator) or its adjoint
+    with the pointwise input factor cin and output factor cout (tensors or
+    None) and the scalar `scale` folded into its launch.  The adjoints write
+    every pixel."""
+    shape = (R.domain if adjoint else R.target).shape
+    run = R._adj if adjoint else R._fwd
     cin = None if cin is None else cin.reshape(-1).contiguous()
     cout = None if cout is None else cout.reshape(-1).contiguous()
 
     def f(x, acc=None, alpha=0.):
-        y = C.apply_rows(x.reshape(1, -1).contiguous(), colscale=cin, rowscale=cout, scale=scale)
-        return _finish(y.reshape(gshape), acc, alpha)
+        y = run(x.reshape(1, -1).contiguous(), colscale=cin, rowscale=cout, scale=scale)
+        return _finish(y.reshape(shape), acc, alpha)
     return f
 
 
@@ -203,12 +159,7 @@ def _lower_chain(ops, adjoint):
                 j += 1
             cin, s_in = _fold(pre)
             cout, s_out = _fold(post)
-            lower_r = _samp
-            if isinstance(op, LOSResponse):
-                lower_r = _los
-            elif isinstance(op, FuncConvolutionOperator):
-                lower_r = _conv
-            fns.append(("fn", lower_r(op, adj, cin, cout, s_in * s_out)))
+            fns.append(("fn", _response(op, adj, cin, cout, s_in * s_out)))
             i = j
             continue
         pw = _pointwise(op)

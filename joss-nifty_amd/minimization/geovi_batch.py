@@ -213,11 +213,6 @@ class _CFStage:
         return Q
 
 
-# a pointwise stage in front of the LOS response rides in the LOS kernels
-# (NFT_FUSE_PTW=0: separate multiplies, for measurement)
-_FUSE_PTW = os.environ.get("NFT_FUSE_PTW", "1") != "0"
-
-
 class _PtwStage:
     def __init__(self, name, args, kwargs):
         from ..pointwise import ptw_dict
@@ -305,9 +300,7 @@ class _LinStage:
             return (V.reshape((k,) + self.dshape) * self.v).reshape((k,) + self.tshape)
         if self.kind == "reshape":
             return V.reshape((k,) + self.tshape)
-        if self.kind == "samp":
-            return self.v._fwd(V.reshape(k, -1))
-        return _los_fwd(self.v, V.reshape(k, -1))
+        return self.v._fwd(V.reshape(k, -1))     # los, samp: the responses' row interface
 
     def vjp(self, _, G):
         k = G.shape[0]
@@ -317,54 +310,7 @@ class _LinStage:
             return (G.reshape((k,) + self.tshape) * self.v).reshape((k,) + self.dshape)
         if self.kind == "reshape":
             return G.reshape((k,) + self.dshape)
-        if self.kind == "samp":
-            return self.v._adj(G.reshape(k, -1)).reshape((k,) + self.dshape)
-        return _los_adj(self.v, G.reshape(k, -1)).reshape((k,) + self.dshape)
-
-
-def _pixel_rows(d, k, a, b):
-    """rows a:b of a pointwise derivative shared (1 row) or one per vector"""
-    if d is None:
-        return None
-    return d.reshape(1, -1) if d.shape[0] == 1 else d.reshape(k, -1)[a:b]
-
-
-def _los_fwd(R, V, d=None, scale=1.0):
-    """scale * R (d * V) row by row; d (the derivative of a pointwise stage in
-    front of R) is applied as the kernel loads the pixels, the scalar of a
-    scaling stage behind R as it stores each line (nft_los_forward_ex: the
-    same product as the separate multiply)."""
-    from ..library.los_response import LOS_KMAX
-    plan = R._box_plan()
-    k = V.shape[0]
-    V = V.contiguous()
-    y = torch.empty((k, R.target.shape[0]), dtype=V.dtype, device=V.device)
-    for a in range(0, k, LOS_KMAX):
-        b = min(k, a + LOS_KMAX)
-        if d is None:
-            _native.los_forward_batched(plan, V[a:b], y[a:b], scale=scale)
-        else:
-            _native.los_forward_ex(plan, V[a:b], y[a:b], colscale=_pixel_rows(d, k, a, b), scale=scale)
-    return y
-
-
-def _los_adj(R, Y, d=None, ys=None):
-    """d * R^T (ys * Y) row by row (d applied as the pixels are stored,
-    nft_los_adjoint_ex; ys, a per-line vector, as the line values are read --
-    the same product as the separate multiply)."""
-    from ..library.los_response import LOS_KMAX
-    plan = R._box_plan()
-    k = Y.shape[0]
-    Y = Y.contiguous()
-    npix = int(np.prod(R.domain.shape))
-    out = torch.empty((k, npix), dtype=Y.dtype, device=Y.device)
-    for a in range(0, k, LOS_KMAX):
-        b = min(k, a + LOS_KMAX)
-        if d is None and ys is None:
-            _native.los_adjoint_batched(plan, Y[a:b], out[a:b])
-        else:
-            _native.los_adjoint_ex(plan, Y[a:b], out[a:b], colscale=ys, rowscale=_pixel_rows(d, k, a, b))
-    return out
+        return self.v._adj(G.reshape(k, -1)).reshape((k,) + self.dshape)
 
 
 class Pipeline:
@@ -436,11 +382,14 @@ class Pipeline:
 
     def _fused_ptw_los(self, i, d, U):
         """stage i pointwise and stage i + 1 the LOS response: the derivative
-        d is folded into the LOS kernel's pixel loads / stores"""
+        d (one row shared by the batch, or one per vector) is folded into the
+        LOS kernel's pixel loads / stores, the scalar of a scaling stage
+        behind the response into its line stores / loads (LOSResponse._fwd /
+        _adj: the same products as the separate multiplies)"""
         if i + 1 >= len(self.stages) or not isinstance(self.stages[i], _PtwStage):
             return False
         nx = self.stages[i + 1]
-        if not (isinstance(nx, _LinStage) and nx.kind == "los" and _FUSE_PTW):
+        if not (isinstance(nx, _LinStage) and nx.kind == "los"):
             return False
         return d.dtype == U.dtype and d.is_contiguous() and d.shape[0] in (1, U.shape[0])
 
@@ -450,7 +399,7 @@ class Pipeline:
         in double, which is the separate multiply's rounding only when the
         vectors are double (fp32 vectors round after every multiply)"""
         if dtype == torch.float64 and j < len(self.stages) and isinstance(self.stages[j], _LinStage) \
-                and self.stages[j].kind == "scale" and _FUSE_PTW:
+                and self.stages[j].kind == "scale":
             return float(self.stages[j].v)
         return None
 
@@ -461,7 +410,7 @@ class Pipeline:
             s, st = self.stages[i], states[i]
             if self._fused_ptw_los(i, st, U):
                 f = self._scalar_after(i + 2, U.dtype)
-                U = _los_fwd(self.stages[i + 1].v, U.reshape(U.shape[0], -1), st, 1.0 if f is None else f)
+                U = self.stages[i + 1].v._fwd(U.reshape(U.shape[0], -1), colscale=st, scale=1.0 if f is None else f)
                 i += 2 if f is None else 3
                 continue
             U = s.jvp(st, U)
@@ -485,12 +434,12 @@ class Pipeline:
                 if ys is None:
                     ys = torch.full((R.target.shape[0],), f, dtype=torch.float64, device=U.device)
                     self._lsc[(i, str(U.device))] = ys
-                U = _los_adj(R, U.reshape(U.shape[0], -1), states[i - 2], ys=ys.to(U.dtype)).reshape(
+                U = R._adj(U.reshape(U.shape[0], -1), colscale=ys.to(U.dtype), rowscale=states[i - 2]).reshape(
                     (U.shape[0],) + self.stages[i - 1].dshape)
                 i -= 3
                 continue
             if i >= 2 and self._fused_ptw_los(i - 1, states[i - 1], U):
-                U = _los_adj(s.v, U.reshape(U.shape[0], -1), states[i - 1]).reshape((U.shape[0],) + s.dshape)
+                U = s.v._adj(U.reshape(U.shape[0], -1), rowscale=states[i - 1]).reshape((U.shape[0],) + s.dshape)
                 i -= 2
                 continue
             U = s.vjp(st, U)

@@ -42,6 +42,7 @@ from ..domain_tuple import DomainTuple
 from ..domains import RGSpace
 from ..field import Field
 from .endomorphic_operator import EndomorphicOperator
+from .middle import ResponseMiddle
 
 
 def conv_gain(space, func):
@@ -248,6 +249,10 @@ class FuncConvolutionOperator(EndomorphicOperator):
                 _native.dot(t.reshape(-1), y.reshape(-1).contiguous(), out=qpart[v, :1])
         return out
 
+    # C is symmetric: both sides of the responses' row interface
+    # (operators/middle.py) are apply_rows
+    _fwd = _adj = apply_rows
+
     def apply(self, x, mode):
         self._check_input(x, mode)
         if x.val.is_complex():
@@ -265,37 +270,6 @@ class FuncConvolutionOperator(EndomorphicOperator):
         diagonal dr (tensor or None) in the first call's column scale and the
         second call's row scale, and the grid weight c (tensor or float) in
         the first call's row scale."""
-        shape = self._shape
-        npix = self._npix
-        drf = None if dr is None else dr.reshape(-1).to(torch.float64).contiguous()
-        scale = float(fct)
-        cv = None
-        if torch.is_tensor(c):
-            cv = c.reshape(-1).expand(npix).to(torch.float64).contiguous()
-        else:
-            scale *= float(c)
-
-        def scales(dt):
-            return drf, cv
-
-        def middle(s, qpart=None, fold=None):
-            """qpart (optional, (k, >= quad_blocks) fp64): per-block partials
-            of the quadratic form s . middle(s), from the data space"""
-            if fold is not None:
-                raise NotImplementedError("convolution middle: the curvature fold runs as its own launch")
-            batched = s.dim() > len(shape)
-            k = s.shape[0] if batched else 1
-            y = self.apply_rows(s.reshape(k, npix), colscale=drf, rowscale=cv, scale=scale, qpart=qpart)
-            out = self.apply_rows(y, rowscale=drf).reshape((k,) + shape)
-            return out if batched else out[0]
-        middle.supports_batch = True
-        middle.supports_fp32 = False
-        middle.supports_fold = False
-        middle.quad_blocks = self.quad_blocks()
-        # what the middle is made of (read-only); named apart from the LOS
-        # middle's `plan` / `scales` (operators/joint_middle.py tells by them)
-        middle.response = self
-        middle.conv_plan = self.conv_plan()
-        middle.conv_scales = scales
-        middle.factor = scale
-        return middle
+        m = ResponseMiddle(self, dr, c, fct, fp32=False)
+        m.conv_plan, m.conv_scales = self.conv_plan(), m.scales_as
+        return m

@@ -9,9 +9,9 @@ periodically."""
 import numpy as np
 import torch
 
-from .. import _native
 from ..domain_tuple import DomainTuple
 from ..domains import RGSpace, UnstructuredDomain
+from .middle import ResponseMiddle
 from .sampling_plan import MAX_ENTRIES, SamplingResponse, interp_points, samp_plan
 
 
@@ -46,49 +46,10 @@ class LinearInterpolator(SamplingResponse):
         middle of a sampling metric J^T D R^T C R D J with pixel-space diagonal
         dr (tensor or None) and data-space weight c (tensor or float) folded
         into the two sampling launches (column / row scales)."""
-        npnt = self.npoints
-        shape = self._domain.shape
-        npix = int(np.prod(shape))
-        if npnt == 0:
+        if self.npoints == 0:
             # no data: the zero map, as a pointwise weight
             from .. import config
-            return torch.zeros(shape, dtype=torch.float64, device=config.device())
-        drf = None if dr is None else dr.reshape(-1).contiguous()
-        scale = float(fct)
-        cv = None
-        if torch.is_tensor(c):
-            cv = c.reshape(-1).expand(npnt).contiguous()
-        else:
-            scale *= float(c)
-        cast = {}
-
-        def scales(dt):
-            # fp32 CG storage (config.set_cg_precision): scales in the input's dtype
-            if dt == torch.float64:
-                return drf, cv
-            if dt not in cast:
-                cast[dt] = (None if drf is None else drf.to(dt), None if cv is None else cv.to(dt))
-            return cast[dt]
-
-        def middle(s, qpart=None, fold=None):
-            """qpart (optional, (k, >= quad_blocks) fp64): per-block partials
-            of the quadratic form s . middle(s), from the data space"""
-            if fold is not None:
-                raise NotImplementedError("sampling middle: the curvature fold runs as its own launch")
-            d, w = scales(s.dtype)
-            batched = s.dim() > len(shape)
-            k = s.shape[0] if batched else 1
-            y = self._fwd(s.reshape(k, npix), colscale=d, rowscale=w, scale=scale, qpart=qpart)
-            out = self._adj(y, rowscale=d).reshape((k,) + tuple(shape))
-            return out if batched else out[0]
-        middle.supports_batch = True
-        middle.supports_fp32 = True
-        middle.supports_fold = False
-        middle.quad_blocks = _native.samp_quad_blocks(self._samp_plan())
-        # what the middle is made of (read-only); named apart from the LOS
-        # middle's `plan` / `scales` (operators/joint_middle.py tells by them)
-        middle.response = self
-        middle.samp_plan = self._samp_plan()
-        middle.samp_scales = scales
-        middle.factor = scale
-        return middle
+            return torch.zeros(self._domain.shape, dtype=torch.float64, device=config.device())
+        m = ResponseMiddle(self, dr, c, fct)
+        m.samp_plan, m.samp_scales = self._samp_plan(), m.scales_as
+        return m

@@ -209,6 +209,10 @@ class SamplingResponse(LinearOperator):
             self._plan = (d, keep)
         return self._plan[0]
 
+    def quad_blocks(self):
+        """qpart columns of `_fwd` (nft_samp_quad_blocks)"""
+        return _native.samp_quad_blocks(self._samp_plan())
+
     def _fwd(self, V, colscale=None, rowscale=None, scale=1.0, qpart=None):
         """rows of V (k, npix) -> (k, npoints), 8 vectors per launch; colscale
         one pixel vector or (k, npix) rows"""

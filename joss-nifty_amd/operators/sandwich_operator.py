@@ -18,6 +18,7 @@ from .chain_operator import ChainOperator
 from .diagonal_operator import DiagonalOperator
 from .endomorphic_operator import EndomorphicOperator
 from .linear_operator import LinearOperator
+from .middle import OperatorMiddle
 from .scaling_operator import ScalingOperator
 
 
@@ -165,18 +166,7 @@ def _chain_fusion(ops, cheese0):
         if fm is not None:
             return core, fm
         mid = ChainOperator.make(left) if len(left) > 0 else None
-        cheese = cheese0
-        tgt = core.target
-
-        def middle(s):
-            from ..field import Field
-            f = Field(tgt, s)
-            if mid is None:
-                r = cheese(f)
-            else:
-                r = mid.adjoint_times(cheese(mid(f)))
-            return r.val * fct if fct != 1. else r.val
-        return core, middle
+        return core, OperatorMiddle(mid, cheese0, core.target, fct)
     if not torch.is_tensor(w):
         w = torch.full(core.target.shape, float(w), dtype=torch.float64, device=core.device)
     else:

@@ -10,7 +10,7 @@ Three metrics are timed the same way, in one process:
   joint    lh_los + lh_counts through the fused joint middle
            (nft_los_adjoint_add)
   generic  the same joint metric with the branch results summed by a generic
-           callable (operators/joint_middle._sum_middle): the fallback for
+           callable (operators/middle.SumMiddle): the fallback for
            mixes without a fused middle
 
 Two figures per metric:
@@ -74,14 +74,14 @@ def chunk_us(ift, cf, R, lh, pos, k, generic=False):
     """(us per iteration as bench.kernel_probe reports it, kernel table)"""
     import torch
     from nifty_amd import _native
-    from nifty_amd.operators.joint_middle import _sum_middle
+    from nifty_amd.operators.middle import SumMiddle
     bench._CARRY_CACHE.clear()   # keyed by the core's id: the metrics share one core
     if not generic:
         kp, it = bench.kernel_probe(ift, cf, R, lh, pos, k)
         return it["us_per_iteration"], kp
     lib = _native.load()
     core, W, shift, XS = bench.probe_setup(ift, lh, pos, k)
-    W = _sum_middle([W.los, W.addw])
+    W = SumMiddle([W.los, W.addw])
     X, Rr, D = XS[:k].clone(), XS[k:2 * k].clone(), XS[2 * k:].clone()
     SC = torch.zeros((k, _native.CG_NSCALARS), dtype=torch.float64, device=X.device)
     SC[:, _native.CG_GAMMA] = 1.0
@@ -103,7 +103,7 @@ def main():
 
     import nifty_amd as ift
     from nifty_amd.minimization.fused_cg import fusable_metric
-    from nifty_amd.operators.joint_middle import _sum_middle
+    from nifty_amd.operators.middle import SumMiddle
     ift.config.set_device("cuda:0")
     cf, R, lh_los, pos, _ = bench.build_problem(ift, args.n, args.nlos, "C3")
     lam = cf.exp()
@@ -122,7 +122,7 @@ def main():
     core_l, W_l, sh_l = fusable_metric(A_los)
     core_j, W_j, sh_j = fusable_metric(A_joint)
     assert callable(W_j) and hasattr(W_j, "los"), "the joint metric did not take the fused joint middle"
-    W_g = _sum_middle([W_j.los, W_j.addw])
+    W_g = SumMiddle([W_j.los, W_j.addw])
     lh_joint = lh_los + lh_cnt
     for name, (core, W, sh, A, lh) in (("los", (core_l, W_l, sh_l, A_los, lh_los)),
                                        ("joint", (core_j, W_j, sh_j, A_joint, lh_joint)),
