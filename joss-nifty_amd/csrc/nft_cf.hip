@@ -12,6 +12,12 @@
 // ascending pixel order, i.e. in exactly the order np.bincount accumulates, so
 // the result is bitwise identical to the reference and run-to-run
 // deterministic (no float atomics).
+//
+// Every sum of this file has a fixed order.  tests/bin_cases.py restates each
+// one in numpy (scatter_seq, scatter_wave, fold_full, fold_half,
+// fold_half_sorted) and tests/test_bin_kernels_gpu.py holds every kernel and
+// instantiation below to its restatement bit for bit; a change of order here
+// has to change it there.
 #include <cstdlib>
 
 #include "nft_api_internal.hpp"
@@ -78,7 +84,9 @@ constexpr int NXCD = 8;
 // bin_scatter_il sums them (lane-strided partials, then the shuffle tree), so
 // the planar and the interleaved folded sums agree bitwise for every item
 // count; without LW every bin is one thread's ascending chain (np.bincount's
-// order, the PowerDistributor's bit-exact adjoint).
+// order, the PowerDistributor's bit-exact adjoint).  The wave sum is
+// scatter_wave of tests/bin_cases.py: lane l adds positions a + l, a + l + 64,
+// ... from +0, then v[l] += v[l + off] for off = 32, 16, 8, 4, 2, 1.
 template <typename T, int K, bool LW = false>
 __global__ __launch_bounds__(256) void bin_scatter_chunk(const T* __restrict__ in, const int* __restrict__ perm,
                                                          const int* __restrict__ offs,
@@ -230,61 +238,16 @@ struct FoldShape {
   long long nin, nout;  // elements per pre item
 };
 
-// fold from point-mirror pair sums on the half grid (last axis h = n/2+1):
-// the sign flips of the first d-1 axes only, in the order of bin_fold_kernel
-template <typename T>
-__global__ __launch_bounds__(256) void bin_fold_half_kernel(const T* __restrict__ in, T* __restrict__ out,
-                                                            FoldShape fs, long long pre, long long nhalf) {
-  const long long tot = pre * fs.nout;
-  const int D = fs.d;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < tot;
-       e += (long long)gridDim.x * blockDim.x) {
-    long long r = e % fs.nout;
-    const long long p = e / fs.nout;
-    long long q[FOLD_MAXD], m[FOLD_MAXD];
-    bool two[FOLD_MAXD];
-#pragma unroll
-    for (int a = FOLD_MAXD - 1; a >= 0; --a) {
-      if (a < D) {
-        q[a] = r % fs.h[a];
-        r /= fs.h[a];
-        m[a] = fs.n[a] - q[a];
-        two[a] = q[a] != 0 && m[a] != q[a];
-      } else {
-        q[a] = m[a] = 0;
-        two[a] = false;
-      }
-    }
-    const T* src = in + p * nhalf;
-    T acc = (T)0;
-#pragma unroll
-    for (int s = 0; s < (1 << (FOLD_MAXD - 1)); ++s) {
-      bool ok = true;
-      long long idx = 0;
-#pragma unroll
-      for (int a = 0; a < FOLD_MAXD; ++a) {
-        if (a >= D) continue;
-        if (a == D - 1) {           // the half axis: no flip
-          idx = idx * fs.h[a] + q[a];
-          continue;
-        }
-        const bool hi = (s >> (FOLD_MAXD - 2 - a)) & 1;
-        ok = ok && (!hi || two[a]);
-        idx = idx * fs.n[a] + (hi ? m[a] : q[a]);
-      }
-      // patterns that flip axes beyond d-1 do not exist
-      for (int a = D - 1; a < FOLD_MAXD - 1; ++a) ok = ok && !((s >> (FOLD_MAXD - 2 - a)) & 1);
-      if (ok) acc += src[idx];
-    }
-    out[e] = acc;
-  }
-}
-
-// The same fold, one workgroup per output row (the last, unflipped axis):
-// the row's <= 2^(d-1) image rows are resolved once per workgroup and the
-// threads stream along them -- no per-element 64-bit div / mod (which bound
-// the element-per-thread kernel above at ~2.5 TB/s).  Summation order and
-// start value as in bin_fold_half_kernel (bitwise).
+// Fold from point-mirror pair sums on the half grid (last axis h = n/2+1):
+// the sign flips of the first d-1 axes only.  This kernel is the order
+// reference of every half-grid fold below: a cell's images are added from +0
+// in ascending s, the bit of axis 0 the most significant (the order of
+// bin_fold_kernel over the flipped axes), an image counting only where every
+// flipped axis has q != 0 and n - q != q; tests/bin_cases.py (fold_half)
+// restates it and the kernels are held to that bit for bit.
+// One workgroup per output row (the last, unflipped axis): the row's
+// <= 2^(d-1) image rows are resolved once per workgroup and the threads stream
+// along them -- no per-element 64-bit div / mod.
 template <typename T>
 __global__ __launch_bounds__(256) void bin_fold_half_rows(const T* __restrict__ in, T* __restrict__ out,
                                                           FoldShape fs, long long nouter, long long nhalf) {
@@ -407,7 +370,7 @@ __global__ __launch_bounds__(256) void bin_fold_half_flat_planar(const T* __rest
 // adjacent: out[cpos[cell] * pre + p] (cpos = inverse of the folded index's
 // stable bin -> cell permutation).  One workgroup per cell row, all pre items
 // per thread (<= 8: one 8 pre-byte store per cell).  Summation order and
-// start value as in bin_fold_half_kernel (bitwise); bin_sum_sorted then sums
+// start value as in bin_fold_half_rows (bitwise); bin_sum_sorted then sums
 // each bin over a contiguous run, in the order of bin_scatter_chunk.
 template <typename T, int PRE>
 __global__ __launch_bounds__(256) void bin_fold_half_sorted(const T* __restrict__ in, T* __restrict__ out,
@@ -582,7 +545,8 @@ __global__ __launch_bounds__(256) void bin_fold_half_flat(const T* __restrict__ 
 // (bin_fold_half_sorted with cpos = NULL: in[cell * PRE + p]): chunks of CH
 // bin-sorted positions as in bin_scatter_chunk, one 8 PRE-byte gather per
 // position for all items (the planar layout gathers PRE cache lines), bins
-// summed in ascending position from 0 (bitwise bin_scatter_chunk).
+// summed in ascending position from 0 (bitwise bin_scatter_chunk with LW;
+// scatter_wave of tests/bin_cases.py per item).
 template <typename T, int PRE, int CH>
 __global__ __launch_bounds__(256) void bin_scatter_il(const T* __restrict__ in, const int* __restrict__ perm,
                                                       const int* __restrict__ offs, const int* __restrict__ cb,
@@ -691,7 +655,9 @@ __global__ __launch_bounds__(256) void bin_scatter_il(const T* __restrict__ in, 
 
 
 // I: index type -- 32-bit when pre * nin < 2^31 (the usual case: cheaper
-// div/mod per element), 64-bit otherwise
+// div/mod per element), 64-bit otherwise.  A cell's images are added from +0
+// in ascending s, the bit of axis 0 the most significant -- the ascending
+// raveled index of the images (fold_full of tests/bin_cases.py).
 template <typename T, typename I>
 __global__ __launch_bounds__(256) void bin_fold_kernel(const T* __restrict__ in, T* __restrict__ out, FoldShape fs,
                                                        long long pre) {
@@ -883,7 +849,6 @@ int nft_bin_fold_half(const void* in, void* out, int64_t pre, int ndim, const in
   // one output per thread (NFT_FOLD_FLAT=0: one workgroup per output row)
   const char* fenv = getenv("NFT_FOLD_FLAT");
   const bool flat = !(fenv && fenv[0] == '0') && tot < (1LL << 31) - 256;
-  constexpr bool rows = true;
   const long long nouter = tot / fs.h[ndim - 1];
   const unsigned rgrid = (unsigned)std::min<long long>(nouter, 1LL << 20);
   if (flat && dtype == 0)
@@ -892,18 +857,12 @@ int nft_bin_fold_half(const void* in, void* out, int64_t pre, int ndim, const in
   else if (flat && dtype == 1)
     hipLaunchKernelGGL(bin_fold_half_flat_planar<float>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream,
                        (const float*)in, (float*)out, fs, (unsigned)tot, nhalf);
-  else if (rows && dtype == 0)
+  else if (dtype == 0)
     hipLaunchKernelGGL(bin_fold_half_rows<double>, dim3(rgrid), dim3(256), 0, stream, (const double*)in,
                        (double*)out, fs, nouter, nhalf);
-  else if (rows && dtype == 1)
+  else if (dtype == 1)
     hipLaunchKernelGGL(bin_fold_half_rows<float>, dim3(rgrid), dim3(256), 0, stream, (const float*)in,
                        (float*)out, fs, nouter, nhalf);
-  else if (dtype == 0)
-    hipLaunchKernelGGL(bin_fold_half_kernel<double>, dim3(nblocks(tot)), dim3(256), 0, stream, (const double*)in,
-                       (double*)out, fs, (long long)pre, nhalf);
-  else if (dtype == 1)
-    hipLaunchKernelGGL(bin_fold_half_kernel<float>, dim3(nblocks(tot)), dim3(256), 0, stream, (const float*)in,
-                       (float*)out, fs, (long long)pre, nhalf);
   else {
     set_last_error("nft_bin_fold_half: bad dtype");
     return NFT_ERR_ARG;
