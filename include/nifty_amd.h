@@ -988,6 +988,36 @@ int nft_conv_space_apply_batched(const nft_conv_space_plan* plan, const void* x,
                                  int nvec, int dtype, double* qpart, int64_t qstride, void* ws, size_t ws_bytes,
                                  hipStream_t stream);
 
+/* ---- tall-skinny Gram kernels (block Lanczos) --------------------------- */
+/* The orthogonalisation of a block W of k vectors (1 <= k <= 8, row b at
+ * W + b * wstride) against a basis V of m >= 1 vectors (row j at V + j *
+ * vstride), all of n >= 1 elements; strides in elements, at least n.  fp64
+ * only: dtype must be 0.  A workgroup owns a tile of nft_gram_tile() elements,
+ * keeps that tile of the k block rows in registers and streams the m basis
+ * rows through it: every element of V is read once per call.  Loads are
+ * 16-byte where V, W are 16-byte aligned and the strides of the operands with
+ * more than one row even, 8-byte otherwise, with the same summation order.  No atomics, no device-global
+ * state, no allocation, no synchronisation: capturable.
+ *
+ * NFT_ERR_ARG (nothing launched) for dtype != 0, a NULL pointer, m < 1, k
+ * outside 1..8, n < 1, a stride below n, a workspace below
+ * nft_gram_workspace(m, k, n), beta other than 0 or 1, or W overlapping V. */
+int nft_gram_tile(void);
+/* workgroups (tiles) of a call over n elements: ceil(n / nft_gram_tile()) */
+int nft_gram_blocks(int64_t n);
+/* bytes of nft_gram_dots' partials: m * k * nft_gram_blocks(n) doubles */
+size_t nft_gram_workspace(int m, int k, int64_t n);
+/* C[j * k + b] = V_j . W_b (device fp64, m * k values): per tile a fixed-order
+ * fp64 sum, the tiles folded in tile order by a second kernel.  C[j, b] is
+ * bitwise the same for any k and any place b of that vector in the block. */
+int nft_gram_dots(const void* V, int64_t vstride, int m, const void* W, int64_t wstride, int k, int64_t n, int dtype,
+                  double* C, void* ws, size_t ws_bytes, hipStream_t stream);
+/* W_b = beta * W_b + sum_j T[j * k + b] * V_j (T: device fp64, m * k values),
+ * j ascending, one fma per term; beta = 0 never reads W.  Row b is bitwise the
+ * same for any k and any place in the block. */
+int nft_gram_axpy(const void* V, int64_t vstride, int m, const double* T, void* W, int64_t wstride, int k, int64_t n,
+                  int dtype, double beta, hipStream_t stream);
+
 /* ---- launch profiler (HIP events) -------------------------------------- */
 /* Between nft_prof_begin and nft_prof_end every hot-path kernel launch
  * records a HIP event on its stream just before the launch; nft_prof_end

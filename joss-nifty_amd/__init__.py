@@ -13,6 +13,7 @@ from .config import update as config_update
 from .domain_tuple import DomainTuple
 from .domains import DOFSpace, Domain, PowerSpace, RGSpace, StructuredDomain, UnstructuredDomain
 from .ducc_dispatch import nthreads, set_nthreads
+from .evidence_lower_bound import estimate_evidence_lower_bound
 from .field import Field
 from .library.correlated_fields import CorrelatedFieldMaker, _SlopeRemover, _SpecialSum, _TwoLogIntegrations
 from .library.correlated_fields_simple import CFJacobian, SimpleCorrelatedField

@@ -126,6 +126,12 @@ SIGNATURES = {
     "nft_prod_jvp_batched": (_i, [_i64, _i64, _p, _d, _d, _p, _i64, _p, _i64, _p, _i64, _p, _i, _p]),
     "nft_prod_vjp_batched": (_i, [_i64, _i64, _p, _d, _d, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _d, _p, _i,
                                   _p]),
+    # tall-skinny Gram kernels of the block-Lanczos solver: fp64, no device-global state
+    "nft_gram_tile": (_i, []),
+    "nft_gram_blocks": (_i, [_i64]),
+    "nft_gram_workspace": (_sz, [_i, _i, _i64]),
+    "nft_gram_dots": (_i, [_p, _i64, _i, _p, _i64, _i, _i64, _i, _p, _p, _sz, _p]),
+    "nft_gram_axpy": (_i, [_p, _i64, _i, _p, _p, _i64, _i, _i64, _i, _d, _p]),
 }
 
 
@@ -932,6 +938,55 @@ def mirror_mix(x, y, shape, split, rows=1, x_stride=0, y_stride=0):
     _check(lib.nft_mirror_mix(ptr(x), int(x_stride), ptr(y), int(y_stride), int(rows), len(shape), sh, int(split),
                               dtype_code(x.dtype), stream_ptr()))
     return y
+
+
+GRAM_KMAX = 8      # block rows per Gram call (csrc/nft_eig.hip)
+
+
+def _gram_rows(name, t):
+    """(rows, n, row stride) of a (rows, n) fp64 device matrix with unit
+    element stride (any row stride); anything else raises"""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise NativeError(f"{name}: nifty_amd hot-path ops run on the GPU only; no CPU fallback exists")
+    if t.dim() != 2 or t.shape[1] < 1 or t.stride(1) != 1:
+        raise NativeError(f"{name}: (rows, n) device rows with unit element stride")
+    return t.shape[0], t.shape[1], (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def gram_dots(V, W, out=None):
+    """C = V W^T, (m, k) fp64 on the device (nft_gram_dots): V (m, n) basis
+    rows, W (k, n) block rows, k <= 8; fixed summation order, C[j, b] bitwise
+    independent of k and of the place b of the vector in the block."""
+    lib = load()
+    m, n, vs = _gram_rows("gram_dots", V)
+    k, n2, wst = _gram_rows("gram_dots", W)
+    if n2 != n:
+        raise ValueError("gram_dots: row lengths differ")
+    if out is None:
+        out = torch.empty((m, k), dtype=torch.float64, device=V.device)
+    elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == m * k):
+        raise NativeError("gram_dots: out is a contiguous fp64 device tensor of m * k values")
+    dt = dtype_code(V.dtype) if V.dtype == W.dtype else -1
+    ws = workspace(lib.nft_gram_workspace(m, k, n), V.device, "gram")
+    _check(lib.nft_gram_dots(ptr(V), vs, m, ptr(W), wst, k, n, dt, ptr(out), ptr(ws), ctypes.c_size_t(ws.numel()),
+                             stream_ptr()))
+    return out
+
+
+def gram_axpy(V, T, W, beta=1.0):
+    """W = beta W + T^T V in place (nft_gram_axpy): V (m, n), T (m, k) fp64
+    device coefficients, W (k, n), k <= 8, beta 0 or 1; j ascending, one fma
+    per term.  W may not overlap V."""
+    lib = load()
+    m, n, vs = _gram_rows("gram_axpy", V)
+    k, n2, wst = _gram_rows("gram_axpy", W)
+    if n2 != n:
+        raise ValueError("gram_axpy: row lengths differ")
+    if not (T.is_cuda and T.dtype == torch.float64 and T.is_contiguous() and tuple(T.shape) == (m, k)):
+        raise NativeError("gram_axpy: T is a contiguous (m, k) fp64 device tensor")
+    dt = dtype_code(V.dtype) if V.dtype == W.dtype else -1
+    _check(lib.nft_gram_axpy(ptr(V), vs, m, ptr(T), ptr(W), wst, k, n, dt, float(beta), stream_ptr()))
+    return W
 
 
 class LaunchProfile:
